@@ -25,8 +25,8 @@ test-core: build-core  ## native C++ unit tests
 test-gpu:              ## GPU numerics + workloads on an MI355X box
 	$(GPURUN) --timeout 900 -- 'timeout -k 10 800 $(PY) -m pytest tests -m gpu -x -q'
 
-bench:                 ## headline training throughput (1 GPU; torchrun for N>1)
-	$(PY) bench.py
+bench:                 ## headline training throughput (1 GPU; torchrun for N>1) + ready trials, ResNet-50
+	$(PY) bench.py --full
 bench-launch:          ## job-start -> all-ranks-ready p50 (compat / fast / fast+zygote)
 	$(PY) bench_launch.py --ranks 1 --trials 10
 

@@ -2,13 +2,18 @@
 """Headline benchmark: a *launched* GPT-2-medium PaddleJob on N MI355X.
 
 BASELINE.json metric: "job-start->all-ranks-ready p50 (s); launched tokens/sec
-at 1/2/4/8 MI355X".  Both halves are measured here, through the operator:
+at 1/2/4/8 MI355X".  Both halves are measured here, through the operator.  A
+plain run (``bench.py --gpus N --steps K --warmup W``) does steps 1 and 3 only
+and prints the throughput record; ``--full`` adds step 2, the other ready
+trials (back to back, ready-to-train, ``compat``), the warm slots' footprint,
+the communication measurements after the timed steps (N > 1) and the secondary
+ResNet-50 job, whose fields are null in a plain run's record:
 
 1. this process starts the native local backend in-process (object store +
    PaddleJob controller in ``fast`` mode + gang scheduler + kubelet-lite exec
    agent with its per-node warm launcher + pdo-kv) — the same C++ code as
    ``pdo-manager --backend=local`` (csrc/core);
-2. **ready p50**: ``--ready-trials`` PaddleJobs of N ``noop`` ranks (one
+2. **ready p50** (``--full``): ``--ready-trials`` PaddleJobs of N ``noop`` ranks (one
    ``amd.com/gpu`` each) are created one after the other; a trial's latency is
    PaddleJob create → the last rank's readiness record in pdo-kv, where a rank
    is ready once its RCCL communicator is up (eager ``device_id`` init, even at
@@ -22,7 +27,8 @@ at 1/2/4/8 MI355X".  Both halves are measured here, through the operator:
    ``pdo-launch --workload gpt2 --model gpt2-medium --batch 64 --seq 1024
    --bench``: W untimed steps, then exactly K timed steps bracketed by barrier +
    device synchronize; each rank publishes its elapsed time to pdo-kv and the
-   MAX over ranks gives the whole-job tokens/s.
+   MAX over ranks gives the whole-job tokens/s.  ``--dump-outputs DIR`` has
+   the ranks write what the last timed step computed as ``DIR/<name>.npy``.
 
 The reference's launch path being emulated is
 controllers/paddlejob_controller.go:277-330 (pod creation → ConfigMap →
@@ -85,6 +91,19 @@ def parse_args(argv=None):
     ap.add_argument("--micro-batch", type=int, default=int(os.environ.get("PDO_MICRO_BATCH", "0")),
                     help="per-rank batch (default 64 sequences for gpt2, 256 images for resnet50)")
     ap.add_argument("--seq", type=int, default=1024)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps the ranks write what the last timed step computed as DIR/<name>.npy "
+                         "(float32): loss, and from rank 0 params / grads — the updated parameter arena and the "
+                         "reduced gradient arena, a fixed seeded 4 Mi-element sample of each when larger "
+                         "(launch/run.py _dump_outputs).  Weights, token stream and sample positions are seeded: "
+                         "two builds given the same arguments are comparable file by file")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline job: the ready / back-to-back / ready-to-train / compat "
+                         "trials (--ready-trials, --b2b-trials, --train-ready-trials, --compat-trials), the warm "
+                         "slots' footprint, the ranks' communication measurements after the timed steps (N > 1) "
+                         "and the secondary ResNet-50 job (--secondary-resnet).  Without it only "
+                         "the launched throughput job runs and those fields of the record are null; "
+                         "--ready-only implies it")
     ap.add_argument("--ready-trials", type=int, default=10)
     ap.add_argument("--compat-trials", type=int, default=3,
                     help="ready trials in the reference-equivalent compat mode (the record's compat_ready)")
@@ -329,6 +348,9 @@ def orchestrate(a):
     from paddle_operator_amd.utils.topology import gpu_count
 
     N = a.gpus
+    if not (a.full or a.ready_only):
+        # a plain run: start the backend, launch the one throughput job, print its record
+        a.ready_trials = a.b2b_trials = a.train_ready_trials = a.compat_trials = a.secondary_resnet = 0
     if not a.micro_batch:
         a.micro_batch = 64 if a.workload == "gpt2" else 256
     detected = 0 if a.cpu else gpu_count()
@@ -362,7 +384,10 @@ def orchestrate(a):
         # slots_per_gpu) up to 2 GPUs; one above, so ranks + slots stay at ≤ 2
         # processes per GPU on a full node
         os.environ.setdefault("PDO_SLOTS_PER_GPU", "3" if N <= 2 else "1")
-    sandbox = tempfile.mkdtemp(prefix="pdo-bench-")
+    # <sandbox>/<mode>/<node>/zygote.sock must fit sockaddr_un's 108 bytes: under a deep
+    # TMPDIR the warm launcher could not bind its socket and would never become ready
+    tmp = tempfile.gettempdir()
+    sandbox = tempfile.mkdtemp(prefix="pdo-bench-", dir=tmp if len(tmp) <= 56 else "/tmp")
     if a.no_warm_slots:
         os.environ["PDO_WARM_SLOTS"] = "0"  # read by the agent when it starts the zygote
     out = {}
@@ -378,7 +403,7 @@ def orchestrate(a):
             out["ready"] = ready_stats(trials) if trials else None
             if trials:
                 log(f"ready p50 {out['ready']['p50']}s over {len(trials)} trials ({N} ranks)")
-            if L.zygote and gpus:
+            if L.zygote and gpus and (a.full or a.ready_only):
                 # the warm slots' resident footprint (HIP context + RCCL code), per GPU
                 st = L.cl.zygote_status()
                 out["warm_slots"] = {node: {d: {k: sl.get(k) for k in ("mem_mb", "mem_mb_before_rccl", "warm_s", "n", "n_ready")}
@@ -413,6 +438,10 @@ def orchestrate(a):
                 out["ready_train"] = ready_stats(tt)
                 log(f"ready-to-train p50 {out['ready_train']['p50']}s over {len(tt)} {a.workload} jobs")
             wl += ["--steps", str(a.steps), "--warmup", str(a.warmup), "--bench", "--timeout", "600"]
+            if not a.full:
+                wl += ["--no-comm-diag"]
+            if a.dump_outputs:
+                wl += ["--dump-outputs", os.path.abspath(a.dump_outputs)]
             t0 = L.launch(name, N, wl, a.ops, gang=gang)
             rs = L.wait_records(name, "bench", N, a.timeout)
             L.finish(name)

@@ -31,6 +31,11 @@ def parse_args(argv=None):
     ap.add_argument("--bench", action="store_true",
                     help="benchmark protocol: --warmup untimed steps, then exactly --steps timed steps bracketed by "
                          "barrier + device synchronize; the record goes to pdo-kv /pdo/<job>/bench/<rank>")
+    ap.add_argument("--no-comm-diag", dest="comm_diag", action="store_false",
+                    help="--bench at more than one rank: skip the communication measurements after the timed steps")
+    ap.add_argument("--dump-outputs", default="",
+                    help="--bench: after the timed steps write what the last step computed (loss, and a fixed seeded "
+                         "sample of the updated parameters and of the gradients) as <dir>/<name>.npy")
     ap.add_argument("--batch", type=int, default=0, help="per-rank micro batch (0 = workload default)")
     ap.add_argument("--seq", type=int, default=1024)
     ap.add_argument("--tiny", action="store_true", help="tiny model variant (CPU tests)")
@@ -196,6 +201,8 @@ def _bench(args, b, jenv, trainer, tokens_per_step, ready_rec) -> int:
         loss = trainer.step()
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and loss is not None:
+        _dump_outputs(args.dump_outputs, b, trainer, loss)
     res = {"rank": b.rank, "world": b.world, "steps": args.steps, "warmup": args.warmup, "seconds": dt,
            "t_timed_start": t_wall0, "tokens_per_step_rank": tokens_per_step,
            "loss": float(loss.detach().float()) if loss is not None else None,
@@ -207,7 +214,7 @@ def _bench(args, b, jenv, trainer, tokens_per_step, ready_rec) -> int:
     if dev.type == "cuda":
         res["gpu_name"] = torch.cuda.get_device_name(dev)
         res["max_mem_gb"] = round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)
-    if dist.is_initialized() and dist.get_world_size() > 1:
+    if args.comm_diag and dist.is_initialized() and dist.get_world_size() > 1:
         res["comm"] = _comm_diag(trainer, fence, dev, dt / max(args.steps, 1))
     print("PDO_BENCH " + json.dumps(res), flush=True)
     kv = jenv.kv_endpoints()
@@ -218,6 +225,37 @@ def _bench(args, b, jenv, trainer, tokens_per_step, ready_rec) -> int:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+DUMP_SAMPLE = 4 << 20  # elements per sampled array: 16 MiB of float32 each
+
+
+def _dump_outputs(out_dir, b, trainer, loss):
+    """What the last timed step left with its caller, as float32 ``.npy``
+    files: the loss it returned (every rank) and, from rank 0, the parameters
+    it updated and the gradients it reduced.  Arenas larger than DUMP_SAMPLE
+    elements are sampled at fixed positions (seeded on the arena's length
+    only), so two builds given the same arguments write comparable files."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{b.rank}" if b.world > 1 else ""
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+    save("loss" + sfx, loss.reshape(1))
+    flat = getattr(trainer, "flat", None)
+    if b.rank != 0 or flat is None:
+        return
+    for name, arena in (("params", flat.params), ("grads", flat.grads)):
+        n = arena.numel()
+        if n > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(n)
+            pos = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+            arena = arena[pos.to(arena.device)]
+        save(name, arena)
 
 
 def _comm_diag(trainer, fence, dev, step_s, nosync_steps=3, iters=10):

@@ -502,12 +502,12 @@ def test_exec_agent_elastic_nproc_per_pod_2(tmp_path):
         cl.stop()
 
 
-def test_zygote_warm_launch_and_kill(tmp_path):
+def test_zygote_warm_launch_and_kill(short_tmp_path):
     """bin/pdo-launch forks ranks from the per-node zygote; a pod kill reaches the rank."""
     pdo_launch = os.path.join(REPO, "bin", "pdo-launch")
     if not os.path.exists(pdo_launch):
         pytest.skip("bin/pdo-launch not built")
-    cl = LocalCluster(mode="fast", agent="exec", sandbox_root=str(tmp_path), zygote=True)
+    cl = LocalCluster(mode="fast", agent="exec", sandbox_root=str(short_tmp_path), zygote=True)
     t_end = time.time() + 120
     while not cl.zygotes_ready() and time.time() < t_end:
         time.sleep(0.05)
@@ -536,7 +536,7 @@ def test_zygote_warm_launch_and_kill(tmp_path):
         cl.stop()
 
 
-def test_zygote_gpu_warm_slot_handoff(tmp_path):
+def test_zygote_gpu_warm_slot_handoff(short_tmp_path):
     """The zygote keeps one warm slot per node GPU; a 1-GPU rank is handed to
     it (the slot becomes the rank), a replacement slot comes up, and requests
     that must not use a slot (opt-out, elastic) take the cold fork.  On a CPU
@@ -545,7 +545,7 @@ def test_zygote_gpu_warm_slot_handoff(tmp_path):
     if not os.path.exists(pdo_launch):
         pytest.skip("bin/pdo-launch not built")
     port = _free_port()
-    cl = LocalCluster(mode="fast", agent="exec", sandbox_root=str(tmp_path), zygote=True,
+    cl = LocalCluster(mode="fast", agent="exec", sandbox_root=str(short_tmp_path), zygote=True,
                       nodes=[{"name": "node0", "gpus": 1}], kv_endpoint=f"127.0.0.1:{port}")
     cl.serve(f"127.0.0.1:{port}")
     cl.start()

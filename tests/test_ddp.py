@@ -155,7 +155,7 @@ def _bench_env():
 
 BENCH_ARGS = ["--model", "gpt2-tiny", "--micro-batch", "2", "--seq", "64", "--steps", "2", "--warmup", "1",
               "--ready-trials", "2", "--cpu", "--ops", "torch", "--compat-trials", "1", "--train-ready-trials", "2",
-              "--b2b-trials", "2"]
+              "--b2b-trials", "2", "--full"]
 
 
 def _json_line(out):
@@ -225,7 +225,7 @@ def test_bench_eight_ranks_virtual_gpus(layout):
     env.pop("PDO_SLOTS_PER_GPU", None)
     args = ["--gpus", "8", "--cpu", "--virtual-gpus", "--workload", "resnet50", "--tiny", "--micro-batch", "2",
             "--steps", "2", "--warmup", "1", "--ready-trials", "2", "--compat-trials", "0", "--train-ready-trials", "1",
-            "--b2b-trials", "1", "--ops", "torch", "--pod-layout", layout]
+            "--b2b-trials", "1", "--ops", "torch", "--pod-layout", layout, "--full"]
     r = subprocess.run([sys.executable, "bench.py"] + args, cwd=REPO, env=env, capture_output=True, text=True,
                        timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -251,7 +251,7 @@ def test_bench_eight_virtual_gpus_gang_and_secondary():
     env.pop("PDO_SLOTS_PER_GPU", None)
     args = ["--gpus", "8", "--cpu", "--virtual-gpus", "--model", "gpt2-tiny", "--micro-batch", "2", "--seq", "64",
             "--steps", "2", "--warmup", "1", "--ready-trials", "1", "--compat-trials", "0", "--train-ready-trials", "0",
-            "--b2b-trials", "0", "--ops", "torch"]
+            "--b2b-trials", "0", "--ops", "torch", "--full"]
     r = subprocess.run([sys.executable, "bench.py"] + args, cwd=REPO, env=env, capture_output=True, text=True,
                        timeout=500)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -384,13 +384,40 @@ def test_broadcast_buffers_one_collective_per_dtype():
 def test_bench_launched_resnet_workload():
     """bench.py --workload resnet50 (configs 2/3 through the operator): images/s record."""
     args = ["--workload", "resnet50", "--tiny", "--micro-batch", "4", "--steps", "2", "--warmup", "1",
-            "--ready-trials", "1", "--cpu"]
+            "--ready-trials", "1", "--cpu", "--full"]
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2"] + args, cwd=REPO, env=_bench_env(),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _json_line(r.stdout)
     assert rec["unit"] == "images/s" and rec["n_gpus"] == 2 and rec["config"]["global_batch"] == 8
     assert abs(rec["value"] - 4 * 2 * 2 / (rec["ms_per_step"] * 2 / 1e3)) / rec["value"] < 1e-2
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """Without --full only the throughput job runs (the trial flags are ignored,
+    their fields null); --steps sets the timed steps; --dump-outputs writes the
+    last timed step's loss and its parameter / gradient arenas as float32 .npy."""
+    import numpy as np
+    out = tmp_path / "dump"
+    args = ["--gpus", "1", "--model", "gpt2-tiny", "--micro-batch", "2", "--seq", "64", "--steps", "3", "--warmup", "1",
+            "--cpu", "--ops", "torch", "--ready-trials", "2", "--dump-outputs", str(out)]
+    r = subprocess.run([sys.executable, "bench.py"] + args, cwd=REPO, env=_bench_env(), capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = _json_line(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["unit"] == "tokens/s" and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 2 * 64 / (rec["ms_per_step"] / 1e3)) / rec["value"] < 1e-2
+    for k in ("ready", "ready_p50_s", "ready_train", "ready_b2b", "compat_ready", "warm_slots"):
+        assert rec[k] is None, (k, rec[k])
+    assert "secondary" not in rec
+    arrays = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert sorted(arrays) == ["grads", "loss", "params"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["loss"].shape == (1,) and float(arrays["loss"][0]) == pytest.approx(rec["final_loss"])
+    assert arrays["params"].size > 1000 and arrays["grads"].size >= arrays["params"].size
+    assert np.abs(arrays["grads"]).max() > 0
 
 
 def test_flat_shadow_scope_cpu():

@@ -67,8 +67,8 @@ def _stop(p):
         p.wait()
 
 
-def test_parked_request_cold_forks_after_deadline(tmp_path):
-    p, path, env = _start(tmp_path, PDO_SLOT_TEST="hang", PDO_SLOT_PARK_S="0.5", PDO_SLOT_WARM_MAX_S="600")
+def test_parked_request_cold_forks_after_deadline(short_tmp_path):
+    p, path, env = _start(short_tmp_path, PDO_SLOT_TEST="hang", PDO_SLOT_PARK_S="0.5", PDO_SLOT_WARM_MAX_S="600")
     try:
         st = zygote.query_status(path)
         assert st["slots"]["0"]["ready"] is False
@@ -88,8 +88,8 @@ def test_parked_request_cold_forks_after_deadline(tmp_path):
         _stop(p)
 
 
-def test_slot_stuck_warming_is_killed_and_counted(tmp_path):
-    p, path, _ = _start(tmp_path, PDO_SLOT_TEST="hang", PDO_SLOT_WARM_MAX_S="0.6")
+def test_slot_stuck_warming_is_killed_and_counted(short_tmp_path):
+    p, path, _ = _start(short_tmp_path, PDO_SLOT_TEST="hang", PDO_SLOT_WARM_MAX_S="0.6")
     try:
         t_end = time.time() + 30
         st = None
@@ -116,8 +116,8 @@ def test_slot_stuck_warming_is_killed_and_counted(tmp_path):
 
 
 @pytest.mark.parametrize("policy", ["handoff", "exit"])
-def test_slot_respawn_policy(tmp_path, policy):
-    p, path, env = _start(tmp_path, PDO_SLOT_TEST="cpu", PDO_SLOT_RESPAWN=policy, PDO_SLOTS_PER_GPU="1")
+def test_slot_respawn_policy(short_tmp_path, policy):
+    p, path, env = _start(short_tmp_path, PDO_SLOT_TEST="cpu", PDO_SLOT_RESPAWN=policy, PDO_SLOTS_PER_GPU="1")
     try:
         t_end = time.time() + 30
         while time.time() < t_end and not (zygote.query_status(path)["slots"].get("0") or {}).get("ready"):
@@ -146,10 +146,10 @@ def test_slot_respawn_policy(tmp_path, policy):
         _stop(p)
 
 
-def test_two_slots_serve_back_to_back_jobs_warm(tmp_path):
+def test_two_slots_serve_back_to_back_jobs_warm(short_tmp_path):
     """PDO_SLOTS_PER_GPU=2: a job arriving while the first job's replacement
     slot is still warming takes the second warm slot instead of parking."""
-    p, path, env = _start(tmp_path, PDO_SLOT_TEST="cpu", PDO_SLOTS_PER_GPU="2")
+    p, path, env = _start(short_tmp_path, PDO_SLOT_TEST="cpu", PDO_SLOTS_PER_GPU="2")
     try:
         t_end = time.time() + 30
         while time.time() < t_end:
@@ -174,16 +174,16 @@ def test_two_slots_serve_back_to_back_jobs_warm(tmp_path):
         _stop(p)
 
 
-def test_back_to_back_stream_dispatch_delay_bounded(tmp_path):
+def test_back_to_back_stream_dispatch_delay_bounded(short_tmp_path):
     """A stream of back-to-back jobs on one GPU while replacement slots warm
     (simulated 1.0 s warm-up, one job every ≈ 0.45 s — the round-5 b2b regime
     scaled down): with the default pool (3 slots at ≤ 2 GPUs) no request parks
     long; the zygote's own stamps (PDO_T_ZYG_RECV / PDO_T_DISPATCH) bound it."""
     env0 = {k: v for k, v in os.environ.items() if k != "PDO_SLOTS_PER_GPU"}
-    path = str(tmp_path / "z.sock")
+    path = str(short_tmp_path / "z.sock")
     e = dict(env0, PYTHONPATH=REPO, PDO_SLOT_TEST="cpu", PDO_SLOT_TEST_WARM_S="1.0")
     p = subprocess.Popen([sys.executable, "-m", "paddle_operator_amd.launch.zygote", "--socket", path,
-                          "--warm-devices", "0"], env=e, stdout=open(tmp_path / "z.log", "w"),
+                          "--warm-devices", "0"], env=e, stdout=open(short_tmp_path / "z.log", "w"),
                          stderr=subprocess.STDOUT)
     try:
         t_end = time.time() + 120
@@ -209,10 +209,10 @@ def test_back_to_back_stream_dispatch_delay_bounded(tmp_path):
         _stop(p)
 
 
-def test_two_slot_pool_parks_under_the_same_stream(tmp_path):
+def test_two_slot_pool_parks_under_the_same_stream(short_tmp_path):
     """The same stream with PDO_SLOTS_PER_GPU=2 parks (the round-5 regression's
     mechanism): warm_s / 2 > the job interval."""
-    p, path, env = _start(tmp_path, PDO_SLOT_TEST="cpu", PDO_SLOT_TEST_WARM_S="1.0", PDO_SLOTS_PER_GPU="2")
+    p, path, env = _start(short_tmp_path, PDO_SLOT_TEST="cpu", PDO_SLOT_TEST_WARM_S="1.0", PDO_SLOTS_PER_GPU="2")
     try:
         t_end = time.time() + 60
         while time.time() < t_end and (zygote.query_status(path)["slots"].get("0") or {}).get("n_ready") != 2:

@@ -8,7 +8,7 @@
 # has arguments); the arguments after ':' are split on spaces:
 #   tests[:K]           pytest -m gpu (-k K when given)
 #   smoke               __graft_entry__.smoke()
-#   'bench:ARGS'        bench.py --gpus 1 --steps 20 --warmup 5 (ARGS replace the defaults)
+#   'bench:ARGS'        bench.py --gpus 1 --steps 20 --warmup 5 --full (ARGS replace the defaults)
 #   'probe:SCRIPT ARGS' python tools/SCRIPT ARGS      (stdout -> NAME/probe_SCRIPT.log)
 #   'prof:SCRIPT ARGS'  rocprofv3 --kernel-trace --stats of python tools/SCRIPT ARGS,
 #                       summarised by tools/prof_summary.py (-> NAME/prof_SCRIPT.md)
@@ -47,7 +47,7 @@ run_step() {
       tail -2 "$O/smoke.log" ;;
     bench)
       BENCH_PASS=$((BENCH_PASS + 1))
-      local b=(--gpus 1 --steps 20 --warmup 5); [[ -n $arg ]] && b=("${A[@]}")
+      local b=(--gpus 1 --steps 20 --warmup 5 --full); [[ -n $arg ]] && b=("${A[@]}")
       local bj=$O/bench.json be=$O/bench.err
       (( BENCH_PASS > 1 )) && { bj=$O/bench$BENCH_PASS.json; be=$O/bench$BENCH_PASS.err; }
       timeout -k 10 600 python bench.py "${b[@]}" > "$bj" 2> "$be" \
