@@ -42,7 +42,8 @@ __global__ __launch_bounds__(256) void bucket_kernel(const Meta* __restrict__ me
   for (long long e = span0 + threadIdx.x; e < span0 + 2048 && e < total; e += 256) {
     const int i = find_tensor(meta, n, e);
     const long long k = e - meta[i].offset;
-    if (k >= meta[i].size) continue;  // alignment padding between tensors
+    // alignment padding between tensors, or (k < 0) below the first offset
+    if (k < 0 || k >= meta[i].size) continue;
     T* t = reinterpret_cast<T*>(meta[i].ptr);
     if (FLATTEN) flat[e] = (T)((float)t[k] * scale);
     else t[k] = flat[e];
