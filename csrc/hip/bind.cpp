@@ -106,6 +106,18 @@ bool colsum_defer(bool on) {
 
 int64_t colsum_pending() { return (int64_t)g_colsum_q.size(); }
 
+// ---------------------------------------------------------------- dropout arguments
+// thr = round(p·65536) in [0, 65535] (0: no dropout, the plain kernels run); seed is
+// the 64-bit Philox key, site / step counter words, offset the group-index base
+// (csrc/hip/philox.h).  Checked here, before any launch.
+static pdo::DropArgs drop_args(int64_t thr, uint64_t seed, int64_t site, int64_t step, uint64_t offset, int C) {
+  TORCH_CHECK(thr >= 0 && thr <= 65535, "dropout: thr must be in [0, 65535], got ", thr);
+  TORCH_CHECK(site >= 0 && site <= 0xFFFFFFFFLL && step >= 0 && step <= 0xFFFFFFFFLL,
+              "dropout: site and step are uint32");
+  TORCH_CHECK(thr == 0 || C % 8 == 0, "dropout: C must be a multiple of 8, got ", C);
+  return pdo::DropArgs::make((uint32_t)thr, seed, (uint32_t)site, (uint32_t)step, offset);
+}
+
 // ---------------------------------------------------------------- layernorm
 std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b, double eps) {
   CHECK_IN(x); CHECK_IN(w); CHECK_IN(b); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(b);
@@ -119,8 +131,13 @@ std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b, 
   return {y, mean, rstd};
 }
 
-std::vector<at::Tensor> add_layernorm_fwd(at::Tensor x, at::Tensor r, at::Tensor w, at::Tensor b, double eps,
-                                          c10::optional<at::Tensor> rbias) {
+// thr > 0: h = x + drop(r + rbias)
+std::vector<at::Tensor> add_layernorm_fwd(at::Tensor x, c10::optional<at::Tensor> r_, at::Tensor w, at::Tensor b,
+                                          double eps, c10::optional<at::Tensor> rbias, int64_t thr, uint64_t seed,
+                                          int64_t site, int64_t step, uint64_t offset) {
+  TORCH_CHECK(r_.has_value(), "add_layernorm_fwd: rbias and dropout apply to the residual branch r, which is "
+              "missing (layernorm_fwd is the LayerNorm without one)");
+  const at::Tensor& r = *r_;
   CHECK_IN(x); CHECK_IN(r); CHECK_IN(w); CHECK_IN(b);
   CHECK_BF16(x); CHECK_BF16(r); CHECK_BF16(w); CHECK_BF16(b);
   TORCH_CHECK(x.dim() == 2 && x.sizes() == r.sizes() && w.numel() == x.size(1) && b.numel() == x.size(1));
@@ -131,21 +148,25 @@ std::vector<at::Tensor> add_layernorm_fwd(at::Tensor x, at::Tensor r, at::Tensor
     rb = bp(*rbias);
   }
   const int N = x.size(0), C = x.size(1);
+  const pdo::DropArgs drop = drop_args(thr, seed, site, step, offset, C);
   auto h = at::empty_like(x);
   auto y = at::empty_like(x);
   auto mean = at::empty({N}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({N}, x.options().dtype(at::kFloat));
   CHECK_RC(pdo::layernorm_fwd(bp(x), bp(r), rb, bp(w), bp(b), bp(h), bp(y), fp(mean), fp(rstd), N, C, (float)eps,
-                              cur_stream()), "add_layernorm_fwd");
+                              cur_stream(), &drop), "add_layernorm_fwd");
   return {h, y, mean, rstd};
 }
 
 // grads (optional): destination tensors for dgamma, dbeta (, drbias) — e.g. the
 // parameters' slices of the flat gradient arena — accumulated in place; the
-// result then holds dx only
+// result then holds dx only.  drop (thr > 0): the result gains ddrop, the gradient
+// of the dropped branch, as its last element; want_dx = false then skips the dx
+// store (dx is returned as an empty tensor)
 std::vector<at::Tensor> ln_bwd_impl(at::Tensor dy, at::Tensor x, at::Tensor w, at::Tensor mean, at::Tensor rstd,
                                     c10::optional<at::Tensor> dres, bool rbias,
-                                    c10::optional<std::vector<at::Tensor>> grads) {
+                                    c10::optional<std::vector<at::Tensor>> grads,
+                                    const pdo::DropArgs* drop = nullptr, bool want_dx = true) {
   CHECK_IN(dy); CHECK_IN(x); CHECK_IN(w); CHECK_IN(mean); CHECK_IN(rstd);
   CHECK_BF16(dy); CHECK_BF16(x); CHECK_BF16(w); CHECK_F32(mean); CHECK_F32(rstd);
   TORCH_CHECK(x.dim() == 2 && dy.sizes() == x.sizes() && w.numel() == x.size(1));
@@ -157,7 +178,13 @@ std::vector<at::Tensor> ln_bwd_impl(at::Tensor dy, at::Tensor x, at::Tensor w, a
     TORCH_CHECK(dres->sizes() == x.sizes());
     dr = bp(*dres);
   }
-  auto dx = at::empty_like(x);
+  const bool dropping = drop && drop->thr;
+  TORCH_CHECK(!rbias || dr, "layernorm_bwd: rbias needs the residual gradient");
+  TORCH_CHECK(!dropping || dr, "layernorm_bwd: dropout needs the residual gradient");
+  TORCH_CHECK(want_dx || dropping, "layernorm_bwd: dx can be skipped only with dropout");
+  auto dx = want_dx ? at::empty_like(x) : at::empty({0}, x.options());
+  at::Tensor ddrop;
+  if (dropping) ddrop = at::empty_like(x);
   const int G = pdo::layernorm_bwd_grid(N);
   const int NA = rbias ? 3 : 2;
   auto part = at::empty({G * NA * C + pdo::colsum_scratch_floats(G, NA * C)}, x.options().dtype(at::kFloat));
@@ -177,13 +204,16 @@ std::vector<at::Tensor> ln_bwd_impl(at::Tensor dy, at::Tensor x, at::Tensor w, a
     out = at::empty({NA, C}, w.options());
     for (int i = 0; i < NA; ++i) co.p[i] = bp(out) + (size_t)i * C;
   }
-  CHECK_RC(pdo::layernorm_bwd(bp(dy), bp(x), bp(w), fp(mean), fp(rstd), dr, bp(dx), fp(part),
-                              fp(part) + (size_t)G * NA * C, co, rbias, N, C, cur_stream(), false), "layernorm_bwd");
+  CHECK_RC(pdo::layernorm_bwd(bp(dy), bp(x), bp(w), fp(mean), fp(rstd), dr, want_dx ? bp(dx) : nullptr, fp(part),
+                              fp(part) + (size_t)G * NA * C, co, rbias, N, C, cur_stream(), false, drop,
+                              dropping ? bp(ddrop) : nullptr), "layernorm_bwd");
   // scratch must follow the partial rows (colsum_or_defer's layout): ld = NA·C
   colsum_or_defer(part, G, NA * C, NA * C, co, grads.has_value());
-  if (grads.has_value()) return {dx};
-  if (rbias) return {dx, out[0], out[1], out[2]};
-  return {dx, out[0], out[1]};
+  std::vector<at::Tensor> res = {dx};
+  if (!grads.has_value())
+    for (int i = 0; i < NA; ++i) res.push_back(out[i]);
+  if (dropping) res.push_back(ddrop);
+  return res;
 }
 
 std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w, at::Tensor mean, at::Tensor rstd,
@@ -193,8 +223,10 @@ std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
 
 std::vector<at::Tensor> layernorm_bwd_add(at::Tensor dy, at::Tensor h, at::Tensor w, at::Tensor mean,
                                           at::Tensor rstd, at::Tensor dres, bool rbias,
-                                          c10::optional<std::vector<at::Tensor>> grads) {
-  return ln_bwd_impl(dy, h, w, mean, rstd, dres, rbias, grads);
+                                          c10::optional<std::vector<at::Tensor>> grads, int64_t thr, uint64_t seed,
+                                          int64_t site, int64_t step, uint64_t offset, bool want_dx) {
+  const pdo::DropArgs drop = drop_args(thr, seed, site, step, offset, (int)h.size(-1));
+  return ln_bwd_impl(dy, h, w, mean, rstd, dres, rbias, grads, &drop, want_dx);
 }
 
 // ---------------------------------------------------------------- bias + gelu
@@ -286,13 +318,17 @@ at::Tensor xent_fused(at::Tensor logits, at::Tensor tgt, at::Tensor inv_cnt, int
 }
 
 // ---------------------------------------------------------------- embedding
-at::Tensor embed_fwd(at::Tensor idx, at::Tensor wte, at::Tensor wpe) {
+// thr > 0: y = drop(wte[idx] + wpe[pos])
+at::Tensor embed_fwd(at::Tensor idx, at::Tensor wte, at::Tensor wpe, int64_t thr, uint64_t seed, int64_t site,
+                     int64_t step, uint64_t offset) {
   CHECK_IN(idx); CHECK_IN(wte); CHECK_IN(wpe); CHECK_I64(idx); CHECK_BF16(wte); CHECK_BF16(wpe);
   TORCH_CHECK(idx.dim() == 2 && wte.dim() == 2 && wpe.dim() == 2 && wte.size(1) == wpe.size(1));
   const int B = idx.size(0), S = idx.size(1), C = wte.size(1);
   TORCH_CHECK(S <= wpe.size(0), "sequence longer than the position table");
+  const pdo::DropArgs drop = drop_args(thr, seed, site, step, offset, C);
   auto y = at::empty({B, S, C}, wte.options());
-  CHECK_RC(pdo::embed_fwd(idx.data_ptr<int64_t>(), bp(wte), bp(wpe), bp(y), B, S, C, cur_stream()), "embed_fwd");
+  CHECK_RC(pdo::embed_fwd(idx.data_ptr<int64_t>(), bp(wte), bp(wpe), bp(y), B, S, C, cur_stream(), &drop),
+           "embed_fwd");
   return y;
 }
 
@@ -1260,18 +1296,22 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.doc() = "paddle_operator_amd HIP/CDNA4 kernels (gfx950)";
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("add_layernorm_fwd", &add_layernorm_fwd, py::arg("x"), py::arg("r"), py::arg("w"), py::arg("b"),
-        py::arg("eps"), py::arg("rbias") = py::none());
+        py::arg("eps"), py::arg("rbias") = py::none(), py::arg("thr") = 0, py::arg("seed") = 0, py::arg("site") = 0,
+        py::arg("step") = 0, py::arg("offset") = 0);
   m.def("layernorm_bwd", &layernorm_bwd, py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),
         py::arg("rstd"), py::arg("grads") = py::none());
   m.def("layernorm_bwd_add", &layernorm_bwd_add, py::arg("dy"), py::arg("h"), py::arg("w"), py::arg("mean"),
-        py::arg("rstd"), py::arg("dres"), py::arg("rbias"), py::arg("grads") = py::none());
+        py::arg("rstd"), py::arg("dres"), py::arg("rbias"), py::arg("grads") = py::none(), py::arg("thr") = 0,
+        py::arg("seed") = 0, py::arg("site") = 0, py::arg("step") = 0, py::arg("offset") = 0,
+        py::arg("want_dx") = true);
   m.def("bias_gelu_fwd", &bias_gelu_fwd);
   m.def("bias_gelu_bwd", &bias_gelu_bwd, py::arg("dy"), py::arg("x"), py::arg("b"), py::arg("db_out") = py::none());
   m.def("bias_grad", &bias_grad, py::arg("dy"), py::arg("out") = py::none());
   m.def("xent_fwd", &xent_fwd);
   m.def("xent_bwd", &xent_bwd);
   m.def("xent_fused", &xent_fused);
-  m.def("embed_fwd", &embed_fwd);
+  m.def("embed_fwd", &embed_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe"), py::arg("thr") = 0,
+        py::arg("seed") = 0, py::arg("site") = 0, py::arg("step") = 0, py::arg("offset") = 0);
   m.def("embed_bwd", &embed_bwd);
   m.def("embed_bwd_sorted", &embed_bwd_sorted);
   m.def("sumsq", &sumsq);

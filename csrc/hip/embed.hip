@@ -1,6 +1,7 @@
 // SPDX-License-Identifier: Apache-2.0
 // Token + position embedding (gfx950).
-// Forward: one wave per token row, y = wte[idx] + wpe[pos] with 16-B vectors.
+// Forward: one wave per token row, y = wte[idx] + wpe[pos] with 16-B vectors
+// (DROP: y = drop(wte[idx] + wpe[pos]), the counter-based mask of philox.h).
 // Backward: d(wte) by f32 atomics shaped as 256 contiguous bytes per wave
 // instruction (one row segment per instruction, the fast atomic shape on
 // MI355X) into a zeroed f32 table, then one vectorised cast to bf16 — or,
@@ -14,9 +15,10 @@ namespace pdo {
 
 constexpr int EMB_SEG = 256;  // sorted rows per segment of the deterministic embedding backward
 
+template <bool DROP>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restrict__ idx, const bf16* __restrict__ wte,
                                                         const bf16* __restrict__ wpe, bf16* __restrict__ y, int N,
-                                                        int S, int C) {
+                                                        int S, int C, DropArgs drop) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= N) return;
@@ -25,7 +27,16 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
   const bf16x8* a = reinterpret_cast<const bf16x8*>(wte + (size_t)tok * C);
   const bf16x8* p = reinterpret_cast<const bf16x8*>(wpe + (size_t)pos * C);
   bf16x8* o = reinterpret_cast<bf16x8*>(y + (size_t)row * C);
-  for (int c8 = lane; c8 < (C >> 3); c8 += 64) o[c8] = to_bf16(to_f32(a[c8]) + to_f32(p[c8]));
+  const int C8 = C >> 3;
+  for (int c8 = lane; c8 < C8; c8 += 64) {
+    f32x8 v = to_f32(a[c8]) + to_f32(p[c8]);
+    if (DROP) {
+      const uint32_t keep = drop_keep_bits(drop, (uint64_t)row * C8 + c8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = (keep >> j) & 1u ? v[j] * drop.scale : 0.f;
+    }
+    o[c8] = to_bf16(v);
+  }
 }
 
 __global__ __launch_bounds__(256) void embed_bwd_wte_kernel(const bf16* __restrict__ dy, const int64_t* __restrict__ idx,
@@ -129,10 +140,16 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restric
   }
 }
 
-int embed_fwd(const int64_t* idx, const bf16* wte, const bf16* wpe, bf16* y, int B, int S, int C, hipStream_t st) {
+int embed_fwd(const int64_t* idx, const bf16* wte, const bf16* wpe, bf16* y, int B, int S, int C, hipStream_t st,
+              const DropArgs* drop) {
   if (C % 8) return -2;
+  if (drop && drop->thr > 65535u) return -6;
   const int N = B * S;
-  embed_fwd_kernel<<<(N + 3) / 4, 256, 0, st>>>(idx, wte, wpe, y, N, S, C);
+  const DropArgs d = drop ? *drop : DropArgs();
+  if (d.thr)
+    embed_fwd_kernel<true><<<(N + 3) / 4, 256, 0, st>>>(idx, wte, wpe, y, N, S, C, d);
+  else
+    embed_fwd_kernel<false><<<(N + 3) / 4, 256, 0, st>>>(idx, wte, wpe, y, N, S, C, d);
   return 0;
 }
 

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "philox.h"
+
 namespace pdo {
 typedef __bf16 bf16;
 
@@ -25,14 +27,20 @@ struct ColOut {
 };
 
 // layernorm.hip
+// drop (optional, thr > 0, needs r): h = x + drop(r + rb) — dropout of the residual
+// branch from the counter-based mask of philox.h; thr == 0 runs the plain kernel
 int layernorm_fwd(const bf16* x, const bf16* r, const bf16* rb, const bf16* w, const bf16* b, bf16* h, bf16* y,
-                  float* mean, float* rstd, int N, int C, float eps, hipStream_t st);
+                  float* mean, float* rstd, int N, int C, float eps, hipStream_t st,
+                  const DropArgs* drop = nullptr);
 int layernorm_bwd_grid(int N);
 // out: where dgamma | dbeta | (drbias) go (ColOut segments of C columns)
 // reduce = false: only the partial rows are written (the caller reduces part later)
 int layernorm_bwd(const bf16* dy, const bf16* x, const bf16* w, const float* mean, const float* rstd,
                   const bf16* dres, bf16* dx, float* part, float* scratch, const ColOut& out, bool rbias, int N,
-                  int C, hipStream_t st, bool reduce = true);
+                  int C, hipStream_t st, bool reduce = true, const DropArgs* drop = nullptr, bf16* ddrop = nullptr);
+// with drop (thr > 0, needs dres and ddrop): dx (may be null then) stays the
+// gradient of the residual stream, ddrop = mask · scale · dx is the gradient of the
+// dropped branch, and drbias sums the masked, scaled value (the bias sits inside the dropout)
 
 // reduce.hip
 int colsum_scratch_floats(int G, int C);
@@ -208,7 +216,9 @@ int xent_bwd(const bf16* logits, const int64_t* tgt, const float* lse, const flo
              bf16* dlogits, int N, int Vp, int V, hipStream_t st);
 
 // embed.hip
-int embed_fwd(const int64_t* idx, const bf16* wte, const bf16* wpe, bf16* y, int B, int S, int C, hipStream_t st);
+// drop (optional, thr > 0): y = drop(wte[idx] + wpe[pos])
+int embed_fwd(const int64_t* idx, const bf16* wte, const bf16* wpe, bf16* y, int B, int S, int C, hipStream_t st,
+              const DropArgs* drop = nullptr);
 int embed_bwd(const bf16* dy, const int64_t* idx, float* acc, bf16* dwte, bf16* dwpe, int B, int S, int C, int Vp,
               int P, hipStream_t st);
 // part: embed_sorted_part_floats(B·S, C) fp32 scratch (partials of runs that cross segments)

@@ -6,18 +6,33 @@
 // computes dx per row and accumulates dgamma/dbeta per lane in registers over
 // a grid-stride row loop; the 4 waves of a block combine through LDS and the
 // per-block partials are summed by the two-level `colsum` (reduce.hip).
+//
+// DROP instantiations: dropout of the residual branch, h = x + drop(r + rbias),
+// from the counter-based mask of philox.h — one Philox call per 16-B vector in
+// the forward, the same call again in the backward, no stored mask.  The
+// DROP = false instantiations are the kernels as they were (the DropArgs
+// argument is last and unread).
 #include "common.h"
 #include "kernels.h"
 
 namespace pdo {
 
-template <int VPL, bool ADD>
+// v scaled where bit j of keep is set, +0 elsewhere
+__device__ __forceinline__ f32x8 drop_apply(f32x8 v, uint32_t keep, float scale) {
+  f32x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = (keep >> j) & 1u ? v[j] * scale : 0.f;
+  return o;
+}
+
+template <int VPL, bool ADD, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16* __restrict__ x, const bf16* __restrict__ r,
                                                      const bf16* __restrict__ rb,
                                                      const bf16* __restrict__ w, const bf16* __restrict__ b,
                                                      bf16* __restrict__ h, bf16* __restrict__ y,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                     int N, int C, float eps) {
+                                                     int N, int C, float eps, DropArgs drop) {
+  static_assert(ADD || !DROP, "dropout applies to the residual branch");
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= N) return;
@@ -32,9 +47,14 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16* __restrict__ x,
     const int c8 = lane + i * 64;
     if (c8 < C8) {
       v[i] = to_f32(xr[c8]);
-      if (ADD) {
+      if (ADD && !DROP) {
         v[i] += to_f32(rr[c8]);
         if (rb) v[i] += to_f32(reinterpret_cast<const bf16x8*>(rb)[c8]);
+      }
+      if (DROP) {
+        f32x8 t = to_f32(rr[c8]);
+        if (rb) t += to_f32(reinterpret_cast<const bf16x8*>(rb)[c8]);
+        v[i] += drop_apply(t, drop_keep_bits(drop, (uint64_t)row * C8 + c8), drop.scale);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) s += v[i][j];
@@ -77,11 +97,15 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16* __restrict__ x,
 
 // NA = 2: partials (dgamma, dbeta); NA = 3: + colsum(dx) — the gradient of a
 // bias folded into the residual branch (h = x + r + rbias).
-template <int VPL, bool ADD, int NA>
+// DROP: `ddrop` = keep ? o·scale : 0 beside dx = o (dx may be null), and the
+// NA = 3 accumulator sums the masked, scaled value (the bias sits inside the dropout).
+template <int VPL, bool ADD, int NA, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x,
                                                      const bf16* __restrict__ w, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const bf16* __restrict__ dres,
-                                                     bf16* __restrict__ dx, float* __restrict__ part, int N, int C) {
+                                                     bf16* __restrict__ dx, float* __restrict__ part, int N, int C,
+                                                     bf16* __restrict__ ddrop, DropArgs drop) {
+  static_assert(ADD || !DROP, "dropout applies to the residual branch");
   constexpr int COLS = 64 * 8 * VPL;
   __shared__ float red[NA * COLS];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -147,8 +171,18 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16* __restrict__ dy
       if (c8 < C8) {
         f32x8 o = (g[i] - s1 - xh[i] * s2) * rs;
         if (ADD) o += rr[i];
-        if (NA == 3) adx[i] += o;
-        reinterpret_cast<bf16x8*>(dx + base)[c8] = to_bf16(o);
+        if (DROP) {
+          // the bias gradient sums ddrop as stored (rounded to bf16): it is the column
+          // sum of the very gradient the branch GEMM's backward reads, as bias_grad
+          // over that tensor would give
+          const bf16x8 od = to_bf16(drop_apply(o, drop_keep_bits(drop, (uint64_t)row * C8 + c8), drop.scale));
+          if (NA == 3) adx[i] += to_f32(od);
+          reinterpret_cast<bf16x8*>(ddrop + base)[c8] = od;
+          if (dx) reinterpret_cast<bf16x8*>(dx + base)[c8] = to_bf16(o);
+        } else {
+          if (NA == 3) adx[i] += o;
+          reinterpret_cast<bf16x8*>(dx + base)[c8] = to_bf16(o);
+        }
       }
     }
   }
@@ -200,15 +234,19 @@ static int vpl_for(int C) {
 }
 
 int layernorm_fwd(const bf16* x, const bf16* r, const bf16* rb, const bf16* w, const bf16* b, bf16* h, bf16* y,
-                  float* mean, float* rstd, int N, int C, float eps, hipStream_t st) {
+                  float* mean, float* rstd, int N, int C, float eps, hipStream_t st, const DropArgs* drop) {
   if (C % 8 != 0 || C > 4096) return -2;
   if (rb && !r) return -4;
+  if (drop && (drop->thr > 65535u || (drop->thr && !r))) return -6;
   const int grid = (N + 3) / 4;
   const int vpl = vpl_for(C);
-  if (r) {
-    LN_DISPATCH(vpl, ln_fwd_kernel<V, true><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps))
+  const DropArgs d = drop ? *drop : DropArgs();
+  if (d.thr) {
+    LN_DISPATCH(vpl, ln_fwd_kernel<V, true, true><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps, d))
+  } else if (r) {
+    LN_DISPATCH(vpl, ln_fwd_kernel<V, true><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps, d))
   } else {
-    LN_DISPATCH(vpl, ln_fwd_kernel<V, false><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps))
+    LN_DISPATCH(vpl, ln_fwd_kernel<V, false><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps, d))
   }
   return 0;
 }
@@ -226,21 +264,31 @@ int layernorm_bwd_grid(int N) {
 // scratch: colsum_scratch_floats(grid, NA*C)
 int layernorm_bwd(const bf16* dy, const bf16* x, const bf16* w, const float* mean, const float* rstd,
                   const bf16* dres, bf16* dx, float* part, float* scratch, const ColOut& out, bool rbias, int N,
-                  int C, hipStream_t st, bool reduce) {
+                  int C, hipStream_t st, bool reduce, const DropArgs* drop, bf16* ddrop) {
   if (C % 8 != 0 || C > 4096) return -2;
   if (rbias && !dres) return -4;
   if (out.seg != C) return -5;
+  if (drop && (drop->thr > 65535u || (drop->thr && (!dres || !ddrop)))) return -6;
+  const DropArgs d = drop ? *drop : DropArgs();
+  if (!d.thr && !dx) return -7;  // only the DROP kernels take a null dx
   const int grid = layernorm_bwd_grid(N);
   const int vpl = vpl_for(C);
   if (vpl > 4) return -3;  // register/LDS budget of the in-block combine
   const int NA = rbias ? 3 : 2;
-  if (rbias) {
-    LN_DISPATCH(vpl, ln_bwd_kernel<V, true, 3><<<grid, 256, 0, st>>>(dy, x, w, mean, rstd, dres, dx, part, N, C))
+#define LN_BWD(ADD_, NA_, DROP_) \
+  LN_DISPATCH(vpl, ln_bwd_kernel<V, ADD_, NA_, DROP_><<<grid, 256, 0, st>>>(dy, x, w, mean, rstd, dres, dx, part, N, C, ddrop, d))
+  if (d.thr && rbias) {
+    LN_BWD(true, 3, true)
+  } else if (d.thr) {
+    LN_BWD(true, 2, true)
+  } else if (rbias) {
+    LN_BWD(true, 3, false)
   } else if (dres) {
-    LN_DISPATCH(vpl, ln_bwd_kernel<V, true, 2><<<grid, 256, 0, st>>>(dy, x, w, mean, rstd, dres, dx, part, N, C))
+    LN_BWD(true, 2, false)
   } else {
-    LN_DISPATCH(vpl, ln_bwd_kernel<V, false, 2><<<grid, 256, 0, st>>>(dy, x, w, mean, rstd, dres, dx, part, N, C))
+    LN_BWD(false, 2, false)
   }
+#undef LN_BWD
   if (reduce) colsum(part, grid, NA * C, NA * C, out, scratch, st);
   return 0;
 }

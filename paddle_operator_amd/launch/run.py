@@ -39,6 +39,11 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=0, help="per-rank micro batch (0 = workload default)")
     ap.add_argument("--seq", type=int, default=1024)
     ap.add_argument("--tiny", action="store_true", help="tiny model variant (CPU tests)")
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="gpt2: embedding and residual dropout probability (quantised to 1/65536; default 0)")
+    ap.add_argument("--attn-dropout", type=float, default=0.0,
+                    help="gpt2: attention-probability dropout (framework SDPA path: slow, not replayable)")
+    ap.add_argument("--dropout-seed", type=int, default=0, help="gpt2: seed of the dropout masks")
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="resnet50: keep the step eager (default on one GPU rank: captured once into a HIP graph "
                          "and replayed, workloads/resnet.py; multi-rank steps stay eager)")
@@ -91,8 +96,10 @@ def run_collective(args, jenv) -> int:
         from ..models.gpt2 import GPT2Config
         from ..train import GPT2Trainer
         cfg = GPT2Config.named("gpt2-tiny" if args.tiny else args.model)
+        cfg.embd_pdrop = cfg.resid_pdrop = args.dropout
+        cfg.attn_pdrop = args.attn_dropout
         seq = min(args.seq, cfg.n_positions)
-        trainer = GPT2Trainer(cfg, args.batch or (2 if args.tiny else 32), seq, dev)
+        trainer = GPT2Trainer(cfg, args.batch or (2 if args.tiny else 32), seq, dev, dropout_seed=args.dropout_seed)
         trainer.sync_initial_weights()
         tokens_per_step = trainer.tokens_per_step()
     elif args.workload == "resnet50":
@@ -105,9 +112,7 @@ def run_collective(args, jenv) -> int:
         st, start_step = ckpt.load_latest(args.ckpt_dir)
         if st is not None:
             if args.workload == "gpt2":
-                trainer.flat.load_params(st["params"])
-                trainer.opt.load_state_dict({k: v.to(dev) if torch.is_tensor(v) else v
-                                             for k, v in st["opt"].items()})
+                trainer.load_state_dict(st, start_step)
             else:
                 trainer.load_state_dict(st)
             log(f"rank {b.rank}: resumed from step {start_step}")
@@ -123,8 +128,6 @@ def run_collective(args, jenv) -> int:
         return _bench(args, b, jenv, trainer, tokens_per_step, rec)
 
     def state():
-        if args.workload == "gpt2":
-            return {"params": trainer.flat.params, "opt": trainer.opt.state_dict()}
         return trainer.state_dict()
 
     step = start_step
@@ -166,6 +169,9 @@ def run_collective(args, jenv) -> int:
     summary = {"rank": b.rank, "world": b.world, "steps": done, "seconds": dt,
                "throughput": tokens_per_step * b.world * done / max(dt, 1e-9), "final_step": step,
                "ready_s": rec["t_ready"] - T_START}
+    if args.workload == "gpt2":
+        summary["dropout"] = args.dropout
+        summary["attn_dropout"] = args.attn_dropout
     print("PDO_DONE " + json.dumps(summary), flush=True)
     if dist.is_initialized():
         dist.barrier()
@@ -211,6 +217,9 @@ def _bench(args, b, jenv, trainer, tokens_per_step, ready_rec) -> int:
            "grad_reduce": getattr(getattr(trainer, "ddp", None), "grad_reduce", None),
            "buckets": len(trainer.flat.buckets) if hasattr(trainer, "flat") else None,
            "hip_graph": getattr(trainer, "_graph", None) is not None}
+    if args.workload == "gpt2":
+        res["dropout"] = args.dropout  # 0.0: the headline is a dropout-free step
+        res["attn_dropout"] = args.attn_dropout
     if dev.type == "cuda":
         res["gpu_name"] = torch.cuda.get_device_name(dev)
         res["max_mem_gb"] = round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)

@@ -16,7 +16,14 @@ MI355X-first rather than a transcription of any reference implementation:
   kernel;
 * every dense projection (forward, input gradient, weight gradient, LM head)
   runs on the hand-written gemm_nt4 / gemm_dw4 kernels; library GEMMs run
-  only for shapes outside their contracts.
+  only for shapes outside their contracts;
+* dropout (``embd_pdrop`` / ``resid_pdrop`` / ``attn_pdrop``, all 0 by default,
+  applied only in training) stores no mask: embedding and residual dropout
+  draw a counter-based mask inside the embedding / add+LayerNorm kernels from
+  (``drop_seed``, ``drop_step``, site, element index) and redraw it in the
+  backward.  With residual dropout on, the branch GEMMs run without their
+  residual epilogue.  At probability 0, or in eval mode, the step runs exactly
+  the dropout-free kernels.
 
 The reference operator has no model code at all; this workload
 is what a PaddleJob launches (``deploy/examples/resnet.yaml:14-19`` pattern).
@@ -41,6 +48,10 @@ class GPT2Config:
     n_layer: int = 24
     n_head: int = 16
     ln_eps: float = 1e-5
+    # dropout probabilities, quantised to 1/65536 (GPT-2 / HF GPT2Config train at 0.1)
+    embd_pdrop: float = 0.0
+    resid_pdrop: float = 0.0
+    attn_pdrop: float = 0.0
     # 128: 50304 rows.  256 (PDO_PAD_VOCAB=256): 50432, full 256-wide tiles, so the
     # LM head's forward / dX GEMMs enter gemm_nt4 and its dW gemm_dw4's full-height tiles
     pad_vocab_to: int = field(default_factory=lambda: int(os.environ.get("PDO_PAD_VOCAB", "128")))
@@ -108,8 +119,10 @@ class Block(nn.Module):
         self.fc = Linear(C, 4 * C)
         self.fc_proj = Linear(4 * C, C)
 
-    def forward(self, x, h, ln_next_w, ln_next_b):
+    def forward(self, x, h, ln_next_w, ln_next_b, drop_attn=None, drop_mlp=None, attn_p=0.0):
         """x: residual stream, h: LN1(x) already computed by the caller.
+        ``drop_attn`` / ``drop_mlp``: residual dropout of the two branches
+        (ops.core.Dropout or None), ``attn_p``: attention-probability dropout.
 
         Returns (x_out, LN_next(x_out)) — the next block's LN1 (or the final LN)
         taken here, so each branch output joins the residual stream inside its
@@ -118,11 +131,11 @@ class Block(nn.Module):
         LayerNorm reads the stream once.
         """
         cfg = self.cfg
-        a = ops.qkv_attention(h, self.qkv.weight, self.qkv.bias, cfg.n_head)
+        a = ops.qkv_attention(h, self.qkv.weight, self.qkv.bias, cfg.n_head, attn_p)
         x, h2 = ops.linear_add_layer_norm(a, self.proj.weight, self.proj.bias, x, self.ln2_w, self.ln2_b,
-                                          cfg.ln_eps)
+                                          cfg.ln_eps, drop_attn)
         return ops.mlp_add_layer_norm(h2, self.fc.weight, self.fc.bias, self.fc_proj.weight, self.fc_proj.bias,
-                                      x, ln_next_w, ln_next_b, cfg.ln_eps)
+                                      x, ln_next_w, ln_next_b, cfg.ln_eps, drop_mlp)
 
 
 class GPT2(nn.Module):
@@ -135,6 +148,10 @@ class GPT2(nn.Module):
         self.blocks = nn.ModuleList([Block(cfg) for _ in range(cfg.n_layer)])
         self.lnf_w = nn.Parameter(torch.ones(C))
         self.lnf_b = nn.Parameter(torch.zeros(C))
+        # dropout stream: the 64-bit key and the training-step counter, set by the
+        # trainer (train.GPT2Trainer) before every forward
+        self.drop_seed = 0
+        self.drop_step = 0
         self.reset_parameters()
 
     @torch.no_grad()
@@ -159,17 +176,27 @@ class GPT2(nn.Module):
                     p.normal_(0.0, s, generator=g)
         self.wte[self.cfg.vocab_size:].zero_()
 
+    def _drop(self, p, site):
+        """The dropout of one site for this step (None: off — eval mode or p == 0).
+        Sites: 0 the embedding, 1 + 2·i block i's attention projection, 2 + 2·i its MLP."""
+        if not self.training or p <= 0.0:
+            return None
+        return ops.dropout_spec(p, self.drop_seed, site, self.drop_step)
+
     def forward(self, idx, targets=None):
         cfg = self.cfg
-        x = ops.embedding(idx, self.wte, self.wpe)
+        d0 = self._drop(cfg.embd_pdrop, 0)
+        attn_p = cfg.attn_pdrop if self.training else 0.0
+        x = ops.embedding(idx, self.wte, self.wpe, d0, masked_grad=True)
         blk0 = self.blocks[0]
-        x, h = ops.layer_norm_res(x, blk0.ln1_w, blk0.ln1_b, cfg.ln_eps)
+        x, h = ops.layer_norm_res(x, blk0.ln1_w, blk0.ln1_b, cfg.ln_eps, d0)
         for i, blk in enumerate(self.blocks):
+            da, dm = self._drop(cfg.resid_pdrop, 1 + 2 * i), self._drop(cfg.resid_pdrop, 2 + 2 * i)
             if i + 1 < len(self.blocks):
                 nb = self.blocks[i + 1]
-                x, h = blk(x, h, nb.ln1_w, nb.ln1_b)
+                x, h = blk(x, h, nb.ln1_w, nb.ln1_b, da, dm, attn_p)
             else:
-                x, h = blk(x, h, self.lnf_w, self.lnf_b)
+                x, h = blk(x, h, self.lnf_w, self.lnf_b, da, dm, attn_p)
         if targets is None:
             return ops.linear(h, self.wte)[..., :cfg.vocab_size]
         return ops.lm_head_xent(h, self.wte, targets, cfg.vocab_size)

@@ -71,6 +71,105 @@ def ref_cross_entropy(logits, target, vocab: int | None = None):
 
 
 # ----------------------------------------------------------------------------
+# counter-based dropout masks (host reference of csrc/hip/philox.h)
+# ----------------------------------------------------------------------------
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 in numpy ``uint64`` arithmetic: ``counter`` = four arrays
+    (or ints) of 32-bit words, ``key`` = two 32-bit ints; returns the four output
+    word arrays (uint64 holding 32-bit values)."""
+    import numpy as np
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & np.uint64(_U32) for c in counter)
+    k0, k1 = int(key[0]) & _U32, int(key[1]) & _U32
+    m0, m1, mask, sh = np.uint64(_PHILOX_M0), np.uint64(_PHILOX_M1), np.uint64(_U32), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c0, m1 * c2  # 32 × 32 → 64 bits: no overflow in uint64
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ np.uint64(k0), p1 & mask, (p0 >> sh) ^ c3 ^ np.uint64(k1), p0 & mask
+        k0, k1 = (k0 + _PHILOX_W0) & _U32, (k1 + _PHILOX_W1) & _U32
+    return c0, c1, c2, c3
+
+
+def philox_keep_mask(shape, thr: int, seed: int, site: int, step: int, offset: int = 0) -> torch.Tensor:
+    """The dropout keep mask of a ``[..., C]`` tensor (C % 8 == 0) as the HIP
+    kernels draw it (csrc/hip/philox.h), built on the host: a bool tensor, True =
+    kept.  One Philox4x32-10 call per group of 8 consecutive elements; key =
+    (low, high) half of the 64-bit ``seed``; counter = (g_lo, g_hi, site, step)
+    with g = ``offset`` + the group's index in the flattened tensor; element j
+    takes output word j >> 1, bits 0-15 (j even) or 16-31 (j odd), and is kept
+    iff that value ≥ ``thr`` = round(p·65536).
+
+    This backs the CPU path of every op that takes ``drop`` and the GPU
+    ``PDO_OPS=torch`` path (mask built here and copied: a parity path, not a fast
+    one), so a CPU fp32 model and the HIP bf16 model drop the same elements."""
+    import numpy as np
+    shape = tuple(shape)
+    n = int(np.prod(shape, dtype=np.int64))
+    if not shape or shape[-1] % 8 or not 0 <= thr <= 65535:
+        raise ValueError(f"philox_keep_mask: last dim % 8 and thr in [0, 65535] required, got {shape}, {thr}")
+    g = (np.arange(n // 8, dtype=np.uint64) + np.uint64(offset & 0xFFFFFFFFFFFFFFFF))  # wraps mod 2^64
+    words = philox4x32_10((g & np.uint64(_U32), g >> np.uint64(32), site, step), (seed & _U32, (seed >> 32) & _U32))
+    w = np.stack(words, axis=1)  # [groups, 4]
+    v = np.stack([w & np.uint64(0xFFFF), w >> np.uint64(16)], axis=2).reshape(-1, 8)  # element j: word j>>1, half j&1
+    return torch.from_numpy(v >= np.uint64(thr)).reshape(shape)
+
+
+class Dropout(tuple):
+    """(thr, scale, seed, site, step): one dropout site of one training step.
+    ``thr`` = round(p·65536) (p is quantised to 1/65536), ``scale`` =
+    65536 / (65536 − thr) in fp32, ``seed`` the 64-bit key, ``site`` the stream
+    id, ``step`` the training-step counter.  Build with ``dropout_spec``."""
+
+    __slots__ = ()
+
+    def __new__(cls, thr, scale, seed, site, step):
+        return tuple.__new__(cls, (int(thr), float(scale), int(seed), int(site), int(step)))
+
+    thr = property(lambda s: s[0])
+    scale = property(lambda s: s[1])
+    seed = property(lambda s: s[2])
+    site = property(lambda s: s[3])
+    step = property(lambda s: s[4])
+
+    def kw(self):
+        """The extension's keyword arguments."""
+        return dict(thr=self[0], seed=self[2], site=self[3], step=self[4])
+
+
+def dropout_thr(p: float) -> int:
+    """round(p·65536) clamped to [0, 65535]."""
+    return max(0, min(65535, int(round(float(p) * 65536.0))))
+
+
+def dropout_spec(p: float, seed: int, site: int, step: int):
+    """The ``drop`` argument of the ops for probability ``p``, or None when p
+    quantises to no dropout (thr == 0: the ops then take their plain paths)."""
+    import numpy as np
+    thr = dropout_thr(p)
+    if thr == 0:
+        return None
+    scale = float(np.float32(65536.0) / np.float32(65536 - thr))
+    return Dropout(thr, scale, seed & 0xFFFFFFFFFFFFFFFF, site & _U32, step & _U32)
+
+
+def _as_drop(drop):
+    if drop is None:
+        return None
+    d = drop if isinstance(drop, Dropout) else Dropout(*drop)
+    return d if d.thr else None
+
+
+def ref_dropout(t: torch.Tensor, drop) -> torch.Tensor:
+    """drop(t) with the host-built mask, in t's dtype (differentiable)."""
+    keep = philox_keep_mask(t.shape, drop.thr, drop.seed, drop.site, drop.step).to(t.device)
+    return torch.where(keep, t * drop.scale, torch.zeros((), dtype=t.dtype, device=t.device))
+
+
+# ----------------------------------------------------------------------------
 # linear with direct-to-arena weight gradient
 # ----------------------------------------------------------------------------
 

@@ -71,9 +71,21 @@ def init_distributed(backend: str | None = None, timeout_s: int = 600) -> DistIn
     return info
 
 
+def derive_dropout_seed(dropout_seed: int, rank: int) -> int:
+    """The 64-bit dropout key of one rank: the splitmix64 finaliser of
+    ``dropout_seed + (rank + 1)·0x9E3779B97F4A7C15`` (mod 2^64).  Deterministic in
+    (dropout_seed, rank), and ranks of one job draw different masks."""
+    m = (1 << 64) - 1
+    z = (int(dropout_seed) + (int(rank) + 1) * 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
 class GPT2Trainer:
     def __init__(self, cfg: GPT2Config, micro_batch: int, seq_len: int, device,
-                 dtype=torch.bfloat16, lr=3e-4, bucket_mb: int | None = None, seed: int = 0):
+                 dtype=torch.bfloat16, lr=3e-4, bucket_mb: int | None = None, seed: int = 0,
+                 dropout_seed: int = 0):
         self.cfg = cfg
         self.B = micro_batch
         self.S = seq_len
@@ -108,6 +120,10 @@ class GPT2Trainer:
         self.opt = FlatAdamW(self.flat, lr=lr)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed + (dist.get_rank() if dist.is_initialized() else 0))
+        # dropout (cfg.*_pdrop): masks are a function of (seed, step, site, element);
+        # drop_step advances once per step() and is part of the checkpoint
+        model.drop_seed = derive_dropout_seed(dropout_seed, dist.get_rank() if dist.is_initialized() else 0)
+        self.drop_step = 0
 
     def sync_initial_weights(self):
         self.ddp.broadcast_params(0)
@@ -121,6 +137,8 @@ class GPT2Trainer:
     def step(self, idx=None, tgt=None):
         if idx is None:
             idx, tgt = self.batch()
+        self.model.drop_step = self.drop_step & 0xFFFFFFFF
+        self.drop_step += 1
         self.flat.zero_grad()
         self.ddp.prepare()
         with self.flat.wt_scope():
@@ -138,6 +156,16 @@ class GPT2Trainer:
 
     def tokens_per_step(self):
         return self.B * self.S
+
+    def state_dict(self):
+        return {"params": self.flat.params, "opt": self.opt.state_dict(), "drop_step": self.drop_step}
+
+    def load_state_dict(self, st, step: int = 0):
+        """``step``: the resumed step number, where the dropout stream starts for a
+        checkpoint written before ``drop_step`` existed."""
+        self.flat.load_params(st["params"])
+        self.opt.load_state_dict({k: v.to(self.device) if torch.is_tensor(v) else v for k, v in st["opt"].items()})
+        self.drop_step = int(st.get("drop_step", step))
 
 
 def now():

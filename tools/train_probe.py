@@ -28,6 +28,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dist", action="store_true", help="init the (RCCL) process group even at world 1")
     ap.add_argument("--bucket-mb", type=int, default=0)
+    # (defaults from the environment so tools/gpu.sh stepab can A/B them as configs)
+    ap.add_argument("--dropout", type=float, default=float(os.environ.get("PDO_PROBE_DROPOUT", "0")),
+                    help="embedding + residual dropout probability")
+    ap.add_argument("--attn-dropout", type=float, default=float(os.environ.get("PDO_PROBE_ATTN_DROPOUT", "0")))
     a = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -42,6 +46,9 @@ def main():
         dev = torch.device("cuda", 0)
         torch.cuda.set_device(dev)
     cfg = GPT2Config.named(a.model)
+    if a.dropout or a.attn_dropout:
+        cfg.embd_pdrop = cfg.resid_pdrop = a.dropout
+        cfg.attn_pdrop = a.attn_dropout
     tr = GPT2Trainer(cfg, a.batch, a.seq, dev, bucket_mb=a.bucket_mb or None)
     tr.sync_initial_weights()
     for _ in range(a.warmup):
@@ -59,7 +66,8 @@ def main():
     print(json.dumps({"model": a.model, "batch": a.batch, "ms_per_step": round(dt * 1e3, 3),
                       "tokens_per_s": round(a.batch * a.seq * world / dt, 1), "world": world,
                       "ddp_enabled": tr.ddp.enabled, "buckets": len(tr.flat.buckets),
-                      "grad_reduce": tr.ddp.grad_reduce, "loss": float(loss)}), flush=True)
+                      "grad_reduce": tr.ddp.grad_reduce, "loss": float(loss), "dropout": a.dropout,
+                      "max_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)}), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
 
