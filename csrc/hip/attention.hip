@@ -361,12 +361,65 @@ __device__ __forceinline__ float rowsum8(bf16x8 p, float acc) {
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(p, p, 6, 7), one, acc, false);
 }
 
+// ----- attention-probability dropout (DROP instantiations; mask of philox.h) -----
+// A 32 × 32 score block is 8 × 8 patches of 4 queries × 4 keys.  Register group
+// g (registers 4g … 4g + 3) of lane (li, hh) is a run of 4 consecutive rows
+// 8g + 4hh … + 3 of the block against the lane's own column li, so the 4 lanes
+// of a quad (li >> 2 and hh equal) share the quad's 4 patches, row patch
+// 2g + hh × column patch li >> 2.  Lane i of the quad draws patch g = i
+// (attn_patch_keep: 16 keep bits, bit 8·kb + w for query word w and key byte
+// kb); quad_keep hands every lane the 4 patches' bits by DPP quad broadcasts,
+// shifted right by ``sh`` so the lane's own column is at bit 0:
+//   query on the lane (forward, dQ): sh = li & 3, key e of group g at bit 8e of t[g];
+//   key on the lane (dK/dV): sh = 8·(li & 3), query e of group g at bit e of t[g].
+// No LDS and no stored mask; all lanes are active at every call (the callers
+// branch wave-uniformly only).
+__device__ __forceinline__ void quad_keep(uint32_t own, int sh, uint32_t (&t)[4]) {
+  t[0] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)own, 0x00, 0xf, 0xf, false) >> sh;
+  t[1] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)own, 0x55, 0xf, 0xf, false) >> sh;
+  t[2] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)own, 0xaa, 0xf, 0xf, false) >> sh;
+  t[3] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)own, 0xff, 0xf, 0xf, false) >> sh;
+}
+// Per-lane dropout state of the kernel bodies.  The plain instantiations get the
+// empty primary templates: they hold nothing, and every statement that touches
+// a member sits behind if constexpr (DROP).
+template <bool DROP>
+struct DropPatch {};  // index of the patch the lane draws for the block at position 0
+template <>
+struct DropPatch<true> {
+  uint64_t g = 0;
+};
+template <bool DROP>
+struct KeepBits {};  // quad_keep's result for one 32 × 32 block
+template <>
+struct KeepBits<true> {
+  uint32_t t[4] = {0u, 0u, 0u, 0u};
+};
+// bit ``pos`` of t as a full-width mask (v_bfe_i32)
+__device__ __forceinline__ uint32_t bit_mask(uint32_t t, int pos) { return (uint32_t)((int32_t)(t << (31 - pos)) >> 31); }
+__device__ __forceinline__ float and_mask(float x, uint32_t m) { return __uint_as_float(__float_as_uint(x) & m); }
+// zero the dropped elements of a packed P fragment (query on the lane):
+// elements 0-3 are keys 0-3 of group ta, elements 4-7 those of group tb
+__device__ __forceinline__ bf16x8 drop8_q(bf16x8 p, uint32_t ta, uint32_t tb) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 u = __builtin_bit_cast(u32x4, p);
+  u[0] &= (bit_mask(ta, 0) & 0xffffu) | (bit_mask(ta, 8) & 0xffff0000u);
+  u[1] &= (bit_mask(ta, 16) & 0xffffu) | (bit_mask(ta, 24) & 0xffff0000u);
+  u[2] &= (bit_mask(tb, 0) & 0xffffu) | (bit_mask(tb, 8) & 0xffff0000u);
+  u[3] &= (bit_mask(tb, 16) & 0xffffu) | (bit_mask(tb, 24) & 0xffff0000u);
+  return __builtin_bit_cast(bf16x8, u);
+}
+
 // Variant bits (A/B in one build, PDO_ATTN_FWDV): 1 = diagonal mask by lane-mask
 // constants (and the fully masked half skipped as −inf), two v_max3 chains
 // for the tile max, packed epilogue; 2 = row sums by v_dot2 over the packed P.
-template <int V>
+// DROP: dropout of P.  The row maximum, the row sum l and lse stay those of the
+// undropped P; dropped elements are zeroed in the packed fragments that feed
+// P·V and 1/(1 − p) joins the final 1/l.
+template <int V, bool DROP = false>
 __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16* __restrict__ out,
-                                              float* __restrict__ lse, int B, int S, int H, float c2, int order) {
+                                              float* __restrict__ lse, int B, int S, int H, float c2, int order,
+                                              const DropArgs& da = DropArgs{}) {
   constexpr bool NEW = V & 1, DOT = V & 2;
   __shared__ __attribute__((aligned(16))) bf16 smem[2 * 2 * TROWS * HD];  // [buf][K|V][64][64]
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, li = lane & 31;
@@ -396,6 +449,10 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
   f32x16 nm16 = zero16();
   const int ntiles = (qb * 128 + 128) / TROWS;
   const int wave_qmax = qb * 128 + w * 32 + 31;
+  // DROP: index of the patch this lane draws for the tile at key 0 (philox.h)
+  DropPatch<DROP> dpatch;
+  if constexpr (DROP)
+    dpatch.g = ((uint64_t)bh * (unsigned)(S >> 2) + (unsigned)(q >> 2)) * (unsigned)(S >> 2) + (unsigned)(2 * (li & 3) + hh);
 
   Stage sk, sv;
   unsigned vo[2];
@@ -513,12 +570,24 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
       }
       const bf16* V0 = Vt + vb0;
       const bf16* V1 = Vt + vb1;
+      // keep bits of the tile's two 32-key blocks (an even wave's second block
+      // on its diagonal tile is fully masked: P = 0 there, no draw)
+      KeepBits<DROP> t0, t1;
+      if constexpr (DROP) {
+        const uint64_t gp = dpatch.g + (unsigned)(key0 >> 2);
+        quad_keep(attn_patch_keep(da, gp), li & 3, t0.t);
+        if (!(NEW && key0 + TROWS - 1 > qb * 128 + w * 32 && !(w & 1))) quad_keep(attn_patch_keep(da, gp + 8), li & 3, t1.t);
+      }
       float la = 0.f, lb = 0.f;
       {
-        const bf16x8 p0 = pack8(s0, 0), p1 = pack8(s1, 0);
+        bf16x8 p0 = pack8(s0, 0), p1 = pack8(s1, 0);
         if constexpr (DOT) {
           la = rowsum8(p0, la);
           lb = rowsum8(p1, lb);
+        }
+        if constexpr (DROP) {
+          p0 = drop8_q(p0, t0.t[0], t0.t[1]);
+          p1 = drop8_q(p1, t1.t[0], t1.t[1]);
         }
         o0 = mfma(tr_frag_v<0>(V0), p0, o0);
         o1 = mfma(tr_frag_v<0>(V1), p0, o1);
@@ -526,10 +595,14 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
         o1 = mfma(tr_frag_v<32>(V1), p1, o1);
       }
       {
-        const bf16x8 p0 = pack8(s0, 1), p1 = pack8(s1, 1);
+        bf16x8 p0 = pack8(s0, 1), p1 = pack8(s1, 1);
         if constexpr (DOT) {
           la = rowsum8(p0, la);
           lb = rowsum8(p1, lb);
+        }
+        if constexpr (DROP) {
+          p0 = drop8_q(p0, t0.t[2], t0.t[3]);
+          p1 = drop8_q(p1, t1.t[2], t1.t[3]);
         }
         o0 = mfma(tr_frag_v<16>(V0), p0, o0);
         o1 = mfma(tr_frag_v<16>(V1), p0, o1);
@@ -549,12 +622,14 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
   bf16* orow = out + ((size_t)(b * S + q) * H + h) * HD;
   if constexpr (NEW) {
     // lt ≥ 1: the key that set m contributes exp2(0)
-    const float inv = __builtin_amdgcn_rcpf(lt);
+    float inv = __builtin_amdgcn_rcpf(lt);
+    if constexpr (DROP) inv *= da.scale;
     store_acc_rows_pk(orow, o0, 0, hh, inv);
     store_acc_rows_pk(orow, o1, 32, hh, inv);
     if (hh == 0) lse[(size_t)bh * S + q] = (m + __builtin_amdgcn_logf(lt)) * LN2;
   } else {
-    const float inv = 1.f / lt;
+    float inv = 1.f / lt;
+    if constexpr (DROP) inv *= da.scale;
     store_acc_rows(orow, o0, 0, hh, inv);
     store_acc_rows(orow, o1, 32, hh, inv);
     if (hh == 0) lse[(size_t)bh * S + q] = (m + log2f(lt)) * LN2;
@@ -574,6 +649,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     int order) {
   attn_fwd_body<V>(qkv, out, lse, B, S, H, c2, order);
 }
+// The DROP kernels (forward, dQ, dK/dV) run at 2 waves per SIMD: under the
+// 168-VGPR cap the Philox rounds spill (forward 113, dQ 13, dK/dV 47 VGPRs);
+// uncapped they take 234 / 177 / 219 VGPRs and no scratch.
+template <int V>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_fwd3_drop_d64(
+    const bf16* __restrict__ qkv, bf16* __restrict__ out, float* __restrict__ lse, int B, int S, int H, float c2,
+    int order, DropArgs da) {
+  attn_fwd_body<V, true>(qkv, out, lse, B, S, H, c2, order, da);
+}
 
 // ============================================================================
 // backward dK / dV: workgroup = 128 keys of one (b,h); loop over query tiles
@@ -581,11 +665,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // V (PDO_ATTN_DKDVV): 1 = each sub-block's 4 Q and 4 dO row fragments read
 // before its first score MFMA (the reads overlap; otherwise every MFMA waits
 // for its own LDS round trip), and the diagonal triangle by lane-mask constants.
-template <int V>
+// DROP: dV = (keep ∘ P · sd)ᵀ dO with the dropout scale sd applied at the store,
+// dS = P ∘ (keep · sd · (dO·V) − delta).  The dP accumulator then starts at 0
+// (the mask cannot multiply a chain that already holds −delta); −delta is read
+// again from the slot after the MFMAs and joins in one FMA, in fp32.
+template <int V, bool DROP = false>
 __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf16* __restrict__ dout,
                                           const float* __restrict__ lse, const float* __restrict__ delta,
                                           bf16* __restrict__ dqkv, int B, int S, int H, float c2,
-                                          float scale, float* __restrict__ dbias_part, int order) {
+                                          float scale, float* __restrict__ dbias_part, int order,
+                                          const DropArgs& da = DropArgs{}) {
   // ring of 3 slots × {Q [64][64] bf16, dO [64][64] bf16, lse·log2e [64] f32, delta [64] f32}
   constexpr int SLOT = 2 * TROWS * HD + 2 * TROWS * 2;  // bf16 units (16896 B)
   __shared__ __attribute__((aligned(16))) bf16 smem[3 * SLOT];
@@ -618,6 +707,11 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
   const int qt0 = (kb * 128) / TROWS;
   const int nqt = S / TROWS;
   const int wave_kmin = kb * 128 + w * 32;
+  // DROP: index of the patch this lane draws for the block at query 0 (philox.h);
+  // a block at query qb0 adds (qb0 / 4)·(S / 4)
+  DropPatch<DROP> dpatch;
+  if constexpr (DROP)
+    dpatch.g = ((uint64_t)bh * (unsigned)(S >> 2) + (unsigned)(2 * (li & 3) + hh)) * (unsigned)(S >> 2) + (unsigned)(key >> 2);
 
   // tile qt → ring slot: Q and dO pieces (2 + 2 per wave) and one stats row per
   // wave (waves 0/2 lse·log2e, 1/3 delta — the pairs write identical bytes), so
@@ -666,9 +760,12 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             sacc[4 * g + e] = l4[e];
-            dpacc[4 * g + e] = d4[e];
+            dpacc[4 * g + e] = DROP ? 0.f : d4[e];
           }
         }
+        KeepBits<DROP> tk;
+        if constexpr (DROP)
+          quad_keep(attn_patch_keep(da, dpatch.g + (uint64_t)(unsigned)(qb0 >> 2) * (unsigned)(S >> 2)), 8 * (li & 3), tk.t);
         if constexpr (V == 1) {
           // two k-steps of fragments in flight (16 VGPRs)
           bf16x8 qa0 = row_frag(Qt, 32 * qs, 0, lane), da0 = row_frag(Dt, 32 * qs, 0, lane);
@@ -698,6 +795,8 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             const int qr = 32 * qs + 8 * g + 4 * hh;
+            f32x4 nd4;
+            if constexpr (DROP) nd4 = *reinterpret_cast<const f32x4*>(DL + qr);  // −delta
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int r = 4 * g + e;
@@ -710,8 +809,14 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
                   p = (q0 + qr + e) < key ? 0.f : p;
                 }
               }
-              sacc[r] = p;
-              dpacc[r] = p * dpacc[r];
+              if constexpr (DROP) {
+                const uint32_t km = bit_mask(tk.t[g], e);
+                sacc[r] = and_mask(p, km);
+                dpacc[r] = p * __builtin_fmaf(and_mask(dpacc[r], km), da.scale, nd4[e]);
+              } else {
+                sacc[r] = p;
+                dpacc[r] = p * dpacc[r];
+              }
             }
           }
         };
@@ -749,15 +854,16 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
   bf16* vrow = krow + (size_t)H * HD;
   store_acc_rows(krow, dk0, 0, hh, scale);
   store_acc_rows(krow, dk1, 32, hh, scale);
-  store_acc_rows(vrow, dv0, 0, hh, 1.f);
-  store_acc_rows(vrow, dv1, 32, hh, 1.f);
+  const float vscale = DROP ? da.scale : 1.f;
+  store_acc_rows(vrow, dv0, 0, hh, vscale);
+  store_acc_rows(vrow, dv1, 32, hh, vscale);
   if (dbias_part) {  // fp32 partial row b·(S/128) + kb of the QKV bias gradient, k and v slots
     float* prow = dbias_part + (size_t)(b * (S / 128) + kb) * (3 * H * HD) + (size_t)h * HD;
     float* red = reinterpret_cast<float*>(smem);
     colsum_acc(dk0, 0, scale, red + w * 128, lane);
     colsum_acc(dk1, 32, scale, red + w * 128, lane);
-    colsum_acc(dv0, 0, 1.f, red + w * 128 + 64, lane);
-    colsum_acc(dv1, 32, 1.f, red + w * 128 + 64, lane);
+    colsum_acc(dv0, 0, vscale, red + w * 128 + 64, lane);
+    colsum_acc(dv1, 32, vscale, red + w * 128 + 64, lane);
     float* const out[2] = {prow + (size_t)H * HD, prow + (size_t)2 * H * HD};
     colsum_finish<2>(red, out, tid);
   }
@@ -773,6 +879,11 @@ template <int V>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_bwd_dkdv3_d64(PDO_DKDV_ARGS) {
   dkdv_body<V>(qkv, dout, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, order);
 }
+template <int V>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_dkdv3_drop_d64(PDO_DKDV_ARGS,
+                                                                                                         DropArgs da) {
+  dkdv_body<V, true>(qkv, dout, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, order, da);
+}
 #undef PDO_DKDV_ARGS
 
 // ============================================================================
@@ -783,11 +894,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // multiples of 16, which the swizzle does not see: the tile loop adds only
 // immediates), the diagonal tile's triangle masked by lane-mask constants and
 // its fully masked 32-key half skipped.
-template <int V>
+// DROP: the same dS = P ∘ (keep · sd · (dO·V) − delta); delta = rowsum(dO ∘ O) is
+// taken from the dropped O and needs no change.
+template <int V, bool DROP = false>
 __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16* __restrict__ dout,
                                         const bf16* __restrict__ o, const float* __restrict__ lse,
                                         float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int S, int H,
-                                        float c2, float scale, float* __restrict__ dbias_part, int order) {
+                                        float c2, float scale, float* __restrict__ dbias_part, int order,
+                                        const DropArgs& da = DropArgs{}) {
   constexpr bool NEW = V & 1;
   __shared__ __attribute__((aligned(16))) bf16 smem[2 * 2 * TROWS * HD];
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, li = lane & 31;
@@ -841,6 +955,10 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
   f32x16 a0 = zero16(), a1 = zero16();
   const int ntiles = (qb * 128 + 128) / TROWS;
   const int wave_qmax = qb * 128 + w * 32 + 31;
+  // DROP: index of the patch this lane draws for the block at key 0 (philox.h)
+  DropPatch<DROP> dpatch;
+  if constexpr (DROP)
+    dpatch.g = ((uint64_t)bh * (unsigned)(S >> 2) + (unsigned)(q >> 2)) * (unsigned)(S >> 2) + (unsigned)(2 * (li & 3) + hh);
 
   Stage sk, sv;
   unsigned vo[2];
@@ -903,6 +1021,8 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
             dp = mfma(row_frag(Vt, 32 * ksub, ks, lane), df[ks], dp);
           }
         }
+        KeepBits<DROP> tk;
+        if constexpr (DROP) quad_keep(attn_patch_keep(da, dpatch.g + (unsigned)((key0 >> 2) + 8 * ksub)), li & 3, tk.t);
         auto softmax_grad = [&](auto masked) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -915,7 +1035,10 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
                 p = kr > q ? 0.f : p;
               }
             }
-            s[r] = p * (dp[r] - dq_delta);  // dS^T
+            if constexpr (DROP)
+              s[r] = p * __builtin_fmaf(and_mask(dp[r], bit_mask(tk.t[r >> 2], 8 * (r & 3))), da.scale, -dq_delta);
+            else
+              s[r] = p * (dp[r] - dq_delta);  // dS^T
           }
         };
         // wave-uniform: only the diagonal 32 × 32 block pays for the mask (NEW: the
@@ -970,6 +1093,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     float scale, float* __restrict__ dbias_part, int order) {
   dq_body<V>(qkv, dout, o, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, order);
 }
+template <int V>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_dq_drop_d64(
+    const bf16* __restrict__ qkv, const bf16* __restrict__ dout, const bf16* __restrict__ o,
+    const float* __restrict__ lse, float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int S, int H, float c2,
+    float scale, float* __restrict__ dbias_part, int order, DropArgs da) {
+  dq_body<V, true>(qkv, dout, o, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, order, da);
+}
 
 // Heaviest-first order (attn_block).  The XCD-grouped order cut the kernels'
 // L2 misses 2-3× (forward TCC_EA0_RDREQ 3.1e6 vs 1.05e7 per call) and won the
@@ -980,7 +1110,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // (removed).
 static int attn_order() { return 0; }
 
-int attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int S, int H, int D, float scale, hipStream_t st) {
+int attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int S, int H, int D, float scale, hipStream_t st,
+             const DropArgs* drop) {
   if (D != HD || S % 128 != 0) return -2;
   // variant 3 (lane-mask diagonal, v_max3 chains, buffer-load staging, v_dot2
   // row sums, packed epilogue): 285.1 / 289.0 vs 302.6 / 303.1 µs for variant 0
@@ -991,6 +1122,14 @@ int attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int S, int H, int D, f
   const float c2 = scale * LOG2E;
   // buffer-load variants address the (b, h) slice with 31-bit byte offsets
   const bool fits = (size_t)S * 3 * H * HD * 2 < (1ull << 31);
+  if (drop && drop->thr) {  // the DROP instantiations of the same two variants
+    if (drop->thr > 255) return -3;
+    if (fits)
+      attn_fwd3_drop_d64<3><<<grid, 256, 0, st>>>(qkv, o, lse, B, S, H, c2, attn_order(), *drop);
+    else
+      attn_fwd3_drop_d64<0><<<grid, 256, 0, st>>>(qkv, o, lse, B, S, H, c2, attn_order(), *drop);
+    return 0;
+  }
   if (fits)
     attn_fwd3_d64<3><<<grid, 256, 0, st>>>(qkv, o, lse, B, S, H, c2, attn_order());
   else
@@ -999,9 +1138,21 @@ int attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int S, int H, int D, f
 }
 
 int attn_bwd(const bf16* dout, const bf16* qkv, const bf16* o, const float* lse, float* delta, bf16* dqkv, int B,
-             int S, int H, int D, float scale, hipStream_t st, float* dbias_part) {
+             int S, int H, int D, float scale, hipStream_t st, float* dbias_part, const DropArgs* drop) {
   if (D != HD || S % 128 != 0) return -2;
   const int grid = B * H * (S / 128);
+  if (drop && drop->thr) {  // the DROP instantiations, in the plain kernels' order and variants
+    if (drop->thr > 255) return -3;
+    if ((size_t)S * 3 * H * HD * 2 < (1ull << 31))
+      attn_bwd_dq_drop_d64<1><<<grid, 256, 0, st>>>(qkv, dout, o, lse, delta, dqkv, B, S, H, scale * LOG2E, scale,
+                                                    dbias_part, attn_order(), *drop);
+    else
+      attn_bwd_dq_drop_d64<0><<<grid, 256, 0, st>>>(qkv, dout, o, lse, delta, dqkv, B, S, H, scale * LOG2E, scale,
+                                                    dbias_part, attn_order(), *drop);
+    attn_bwd_dkdv3_drop_d64<1><<<grid, 256, 0, st>>>(qkv, dout, lse, delta, dqkv, B, S, H, scale * LOG2E, scale,
+                                                     dbias_part, attn_order(), *drop);
+    return 0;
+  }
   // dQ first: it also produces delta = rowsum(dO ∘ O), which dK/dV reads
   // variant 1: forward + backward 772.7 / 769.1 vs 786.9 / 784.3 µs with
   // variant 0 (tools/attn_ab.sh), which remains for slices past 31-bit buffer offsets

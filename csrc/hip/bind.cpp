@@ -1090,21 +1090,34 @@ at::Tensor maxpool3s2_bwd(at::Tensor dy, at::Tensor arg, int64_t H, int64_t W) {
 }
 
 // ---------------------------------------------------------------- attention
-std::vector<at::Tensor> attn_fwd(at::Tensor qkv, int64_t n_head) {
+// thr = thr8 = round(p·256) in [0, 255] (0: no dropout, the plain kernels run): attention
+// dropout is quantised to 1/256 and draws one Philox call per 4 × 4 patch (csrc/hip/philox.h)
+static pdo::DropArgs attn_drop_args(int64_t thr, uint64_t seed, int64_t site, int64_t step) {
+  TORCH_CHECK(thr >= 0 && thr <= 255, "attention dropout: thr must be in [0, 255], got ", thr);
+  TORCH_CHECK(site >= 0 && site <= 0xFFFFFFFFll && step >= 0 && step <= 0xFFFFFFFFll,
+              "attention dropout: site and step are uint32");
+  return pdo::DropArgs::make_attn((uint32_t)thr, seed, (uint32_t)site, (uint32_t)step);
+}
+
+std::vector<at::Tensor> attn_fwd(at::Tensor qkv, int64_t n_head, int64_t thr, uint64_t seed, int64_t site,
+                                 int64_t step) {
   CHECK_IN(qkv); CHECK_BF16(qkv);
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) % (3 * n_head) == 0);
   const int B = qkv.size(0), S = qkv.size(1), C = qkv.size(2) / 3, H = n_head, D = C / H;
   TORCH_CHECK(D == 64 && S % 128 == 0, "attn_fwd supports head_dim 64 and seq % 128 == 0");
   auto o = at::empty({B, S, C}, qkv.options());
   auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
-  CHECK_RC(pdo::attn_fwd(bp(qkv), bp(o), fp(lse), B, S, H, D, 1.f / std::sqrt((float)D), cur_stream()), "attn_fwd");
+  const pdo::DropArgs drop = attn_drop_args(thr, seed, site, step);
+  CHECK_RC(pdo::attn_fwd(bp(qkv), bp(o), fp(lse), B, S, H, D, 1.f / std::sqrt((float)D), cur_stream(), &drop),
+           "attn_fwd");
   return {o, lse};
 }
 
 // dqkv, plus (with_bias_grad) the QKV bias gradient reduced from the kernels'
 // fp32 column partials — accumulated into db_out when given, else returned
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor o, at::Tensor lse, int64_t n_head,
-                                 bool with_bias_grad, c10::optional<at::Tensor> db_out) {
+                                 bool with_bias_grad, c10::optional<at::Tensor> db_out, int64_t thr, uint64_t seed,
+                                 int64_t site, int64_t step) {
   CHECK_IN(dout); CHECK_IN(qkv); CHECK_IN(o); CHECK_IN(lse);
   CHECK_BF16(dout); CHECK_BF16(qkv); CHECK_BF16(o); CHECK_F32(lse);
   const int B = qkv.size(0), S = qkv.size(1), C = qkv.size(2) / 3, H = n_head, D = C / H;
@@ -1116,8 +1129,10 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor o, 
   at::Tensor part;
   if (with_bias_grad)
     part = at::empty({(int64_t)G * NC + pdo::colsum_scratch_floats(G, NC)}, qkv.options().dtype(at::kFloat));
+  const pdo::DropArgs drop = attn_drop_args(thr, seed, site, step);
   CHECK_RC(pdo::attn_bwd(bp(dout), bp(qkv), bp(o), fp(lse), fp(delta), bp(dqkv), B, S, H, D,
-                         1.f / std::sqrt((float)D), cur_stream(), with_bias_grad ? fp(part) : nullptr), "attn_bwd");
+                         1.f / std::sqrt((float)D), cur_stream(), with_bias_grad ? fp(part) : nullptr, &drop),
+           "attn_bwd");
   if (!with_bias_grad) return {dqkv};
   at::Tensor db;
   pdo::ColOut co;
@@ -1390,9 +1405,11 @@ PYBIND11_MODULE(_pdo_hip, m) {
         py::arg("w"), py::arg("b"), py::arg("dw_into") = py::none(), py::arg("db_into") = py::none());
   m.def("maxpool3s2_bwd", &maxpool3s2_bwd);
   m.def("gap_bwd", &gap_bwd);
-  m.def("attn_fwd", &attn_fwd);
+  m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("n_head"), py::arg("thr") = 0, py::arg("seed") = 0,
+        py::arg("site") = 0, py::arg("step") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"), py::arg("n_head"),
-        py::arg("with_bias_grad") = false, py::arg("db_out") = py::none());
+        py::arg("with_bias_grad") = false, py::arg("db_out") = py::none(), py::arg("thr") = 0, py::arg("seed") = 0,
+        py::arg("site") = 0, py::arg("step") = 0);
   m.def("scale_", &scale_);
   m.def("scale_dev_", &scale_dev_);
   m.def("fold_zero", &fold_zero);

@@ -241,11 +241,16 @@ int adamw_flat(bf16* p, const bf16* g, float* master, float* m1, float* m2, cons
                float bc2, float grad_scale, float clip, hipStream_t st);
 
 // attention.hip  (qkv: [B, S, 3, H, D] bf16; o: [B, S, H, D]; lse: [B, H, S] f32)
-int attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int S, int H, int D, float scale, hipStream_t st);
+// drop (optional, thr = thr8 > 0, DropArgs::make_attn): attention-probability dropout
+// from the 4 × 4-patch mask of philox.h inside the kernels; thr == 0 runs the plain kernels.
+// lse is that of the undropped softmax.  The backward takes the forward's drop.
+int attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int S, int H, int D, float scale, hipStream_t st,
+             const DropArgs* drop = nullptr);
 // dbias_part (optional): fp32 [B·S/128][3·H·64] column partial sums of dqkv
 // (the QKV bias gradient before its final reduction)
 int attn_bwd(const bf16* dout, const bf16* qkv, const bf16* o, const float* lse, float* delta, bf16* dqkv, int B,
-             int S, int H, int D, float scale, hipStream_t st, float* dbias_part = nullptr);
+             int S, int H, int D, float scale, hipStream_t st, float* dbias_part = nullptr,
+             const DropArgs* drop = nullptr);
 
 // bucket.hip (DDP helpers).  bucket_copy: dtype 0 = bf16, 1 = f32; dev_meta is
 // n × {ptr, numel, offset} (int64) in device memory; flatten: flat[off+k] = scale·t[k],

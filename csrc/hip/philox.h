@@ -13,6 +13,23 @@
 // are multiplied by scale = 65536 / (65536 − thr).  The host reference is
 // paddle_operator_amd.ops.core.philox_keep_mask.
 //
+// Attention-probability dropout (csrc/hip/attention.hip) draws from the same
+// generator with its own element assignment, independent of any kernel's
+// tiling.  One Philox call serves a patch of 4 queries × 4 keys of one (b, h):
+// counter = (g_lo, g_hi, site, step) with the 64-bit patch index
+//   g = ((b·H + h)·(S/4) + q/4)·(S/4) + k/4,
+// key as above.  Element (q, k) takes output word q % 4, bits 8·(k % 4) …
+// 8·(k % 4) + 7, and is kept iff that byte ≥ thr8 = round(p·256): for attention
+// p is quantised to 1/256 (1/65536 at the other sites).  Kept probabilities are
+// multiplied by scale = 256 / (256 − thr8).  Sites: 0x10000 + layer, disjoint
+// from 0 (embedding) and 1 + 2i / 2 + 2i (block i's residual branches).
+// A lane of the flash kernels holds one query and runs of 4 consecutive keys
+// (forward, dQ) or one key and runs of 4 consecutive queries (dK/dV), so one
+// call per lane covers a 32 × 32 score block: the four lanes of a quad each
+// draw one of the quad's four patches, reduce it to 16 keep bits
+// (attn_patch_keep) and exchange them by DPP quad permutes.  The host reference
+// is paddle_operator_amd.ops.core.philox_attn_keep_mask.
+//
 // DropArgs travels by value as a kernel argument: a captured (graph-replayed)
 // step would freeze seed / step / site / offset at their captured values and
 // repeat one mask; the GPT-2 step is launched eagerly.
@@ -22,11 +39,13 @@
 namespace pdo {
 
 struct DropArgs {
-  uint32_t thr = 0;    // 0 = no dropout (callers dispatch to the plain kernels)
-  float scale = 1.f;   // 65536 / (65536 − thr), fp32, computed on the host
+  // 0 = no dropout (callers dispatch to the plain kernels); round(p·65536) at the
+  // LayerNorm / embedding sites, thr8 = round(p·256) for attention
+  uint32_t thr = 0;
+  float scale = 1.f;   // 65536 / (65536 − thr), or 256 / (256 − thr8): fp32, computed on the host
   uint32_t key0 = 0, key1 = 0;  // seed low / high
   uint32_t site = 0, step = 0;
-  uint64_t offset = 0;  // added to the group index, in groups of 8 elements
+  uint64_t offset = 0;  // added to the group index, in groups of 8 elements (unused by attention)
 
   static DropArgs make(uint32_t thr, uint64_t seed, uint32_t site, uint32_t step, uint64_t offset) {
     DropArgs d;
@@ -37,6 +56,17 @@ struct DropArgs {
     d.site = site;
     d.step = step;
     d.offset = offset;
+    return d;
+  }
+  // attention: thr = thr8 in [0, 255], scale = 256 / (256 − thr8), no offset
+  static DropArgs make_attn(uint32_t thr8, uint64_t seed, uint32_t site, uint32_t step) {
+    DropArgs d;
+    d.thr = thr8;
+    d.scale = 256.f / (float)(256u - thr8);
+    d.key0 = (uint32_t)seed;
+    d.key1 = (uint32_t)(seed >> 32);
+    d.site = site;
+    d.step = step;
     return d;
   }
 };
@@ -72,6 +102,25 @@ __device__ __forceinline__ uint32_t drop_keep_bits(const DropArgs& d, uint64_t g
   for (int j = 0; j < 8; ++j) {
     const uint32_t v = (j & 1) ? (p.w[j >> 1] >> 16) : (p.w[j >> 1] & 0xFFFFu);
     keep |= (v >= d.thr ? 1u : 0u) << j;
+  }
+  return keep;
+}
+
+// The 16 keep bits of attention patch g: bit 8·kb + w = element (query word w,
+// key byte kb) kept.  The four bytes of a word are compared at once: with
+// x7 = x & 0x7f per byte, bit 7 of x7 + (0x80 − (thr & 0x7f)) is x7 ≥ thr & 0x7f
+// (the sum is at most 0xff: no carry between bytes), and byte ≥ thr is that
+// bit OR the byte's own bit 7 for thr < 128, AND for thr ≥ 128.  thr in [1, 255].
+__device__ __forceinline__ uint32_t attn_patch_keep(const DropArgs& d, uint64_t g) {
+  const Philox4 p = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), d.site, d.step, d.key0, d.key1);
+  const uint32_t add = (0x80u - (d.thr & 0x7fu)) * 0x01010101u;
+  const uint32_t any = d.thr < 128u ? 0xffffffffu : 0u;
+  uint32_t keep = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint32_t x = p.w[w], y = (x & 0x7f7f7f7fu) + add;
+    const uint32_t ge = (x & y) | ((x | y) & any);  // bit 7 of every byte
+    keep |= (ge & 0x80808080u) >> (7 - w);
   }
   return keep;
 }

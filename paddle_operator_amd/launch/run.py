@@ -42,7 +42,8 @@ def parse_args(argv=None):
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="gpt2: embedding and residual dropout probability (quantised to 1/65536; default 0)")
     ap.add_argument("--attn-dropout", type=float, default=0.0,
-                    help="gpt2: attention-probability dropout (framework SDPA path: slow, not replayable)")
+                    help="gpt2: attention-probability dropout inside the flash-attention kernels (quantised to 1/256; "
+                         "default 0)")
     ap.add_argument("--dropout-seed", type=int, default=0, help="gpt2: seed of the dropout masks")
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="resnet50: keep the step eager (default on one GPU rank: captured once into a HIP graph "

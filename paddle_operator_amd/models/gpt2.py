@@ -21,8 +21,9 @@ MI355X-first rather than a transcription of any reference implementation:
   applied only in training) stores no mask: embedding and residual dropout
   draw a counter-based mask inside the embedding / add+LayerNorm kernels from
   (``drop_seed``, ``drop_step``, site, element index) and redraw it in the
-  backward.  With residual dropout on, the branch GEMMs run without their
-  residual epilogue.  At probability 0, or in eval mode, the step runs exactly
+  backward; attention-probability dropout does the same inside the
+  flash-attention kernels, per (b, h, q, k).  With residual dropout on, the
+  branch GEMMs run without their residual epilogue.  At probability 0, or in eval mode, the step runs exactly
   the dropout-free kernels.
 
 The reference operator has no model code at all; this workload
@@ -119,10 +120,11 @@ class Block(nn.Module):
         self.fc = Linear(C, 4 * C)
         self.fc_proj = Linear(4 * C, C)
 
-    def forward(self, x, h, ln_next_w, ln_next_b, drop_attn=None, drop_mlp=None, attn_p=0.0):
+    def forward(self, x, h, ln_next_w, ln_next_b, drop_attn=None, drop_mlp=None, drop_prob=None):
         """x: residual stream, h: LN1(x) already computed by the caller.
         ``drop_attn`` / ``drop_mlp``: residual dropout of the two branches
-        (ops.core.Dropout or None), ``attn_p``: attention-probability dropout.
+        (ops.core.Dropout or None), ``drop_prob``: the spec of the
+        attention-probability dropout (ops.attn_dropout_spec or None).
 
         Returns (x_out, LN_next(x_out)) — the next block's LN1 (or the final LN)
         taken here, so each branch output joins the residual stream inside its
@@ -131,7 +133,7 @@ class Block(nn.Module):
         LayerNorm reads the stream once.
         """
         cfg = self.cfg
-        a = ops.qkv_attention(h, self.qkv.weight, self.qkv.bias, cfg.n_head, attn_p)
+        a = ops.qkv_attention(h, self.qkv.weight, self.qkv.bias, cfg.n_head, drop=drop_prob)
         x, h2 = ops.linear_add_layer_norm(a, self.proj.weight, self.proj.bias, x, self.ln2_w, self.ln2_b,
                                           cfg.ln_eps, drop_attn)
         return ops.mlp_add_layer_norm(h2, self.fc.weight, self.fc.bias, self.fc_proj.weight, self.fc_proj.bias,
@@ -183,20 +185,27 @@ class GPT2(nn.Module):
             return None
         return ops.dropout_spec(p, self.drop_seed, site, self.drop_step)
 
+    def _drop_attn(self, layer):
+        """Attention-probability dropout of block ``layer`` for this step (None: off).
+        Sites ``ops.ATTN_SITE0`` + layer; p is quantised to 1/256 (csrc/hip/philox.h)."""
+        if not self.training or self.cfg.attn_pdrop <= 0.0:
+            return None
+        return ops.attn_dropout_spec(self.cfg.attn_pdrop, self.drop_seed, ops.ATTN_SITE0 + layer, self.drop_step)
+
     def forward(self, idx, targets=None):
         cfg = self.cfg
         d0 = self._drop(cfg.embd_pdrop, 0)
-        attn_p = cfg.attn_pdrop if self.training else 0.0
         x = ops.embedding(idx, self.wte, self.wpe, d0, masked_grad=True)
         blk0 = self.blocks[0]
         x, h = ops.layer_norm_res(x, blk0.ln1_w, blk0.ln1_b, cfg.ln_eps, d0)
         for i, blk in enumerate(self.blocks):
             da, dm = self._drop(cfg.resid_pdrop, 1 + 2 * i), self._drop(cfg.resid_pdrop, 2 + 2 * i)
+            dp = self._drop_attn(i)
             if i + 1 < len(self.blocks):
                 nb = self.blocks[i + 1]
-                x, h = blk(x, h, nb.ln1_w, nb.ln1_b, da, dm, attn_p)
+                x, h = blk(x, h, nb.ln1_w, nb.ln1_b, da, dm, dp)
             else:
-                x, h = blk(x, h, self.lnf_w, self.lnf_b, da, dm, attn_p)
+                x, h = blk(x, h, self.lnf_w, self.lnf_b, da, dm, dp)
         if targets is None:
             return ops.linear(h, self.wte)[..., :cfg.vocab_size]
         return ops.lm_head_xent(h, self.wte, targets, cfg.vocab_size)

@@ -13,7 +13,8 @@ from .core import (  # noqa: F401
     _HIP_DW, _NT_ALL, _arena_grads, _direct_ok, _fwd_gemm, _input_grad, _signal_ready, _splitk, _weight_grad,
     _weight_grad_lib, _workspace, deferred_reductions, flush_deferred, linear, ref_attention, ref_bias_gelu,
     ref_cross_entropy, ref_layer_norm, transpose, use_hip,
-    Dropout, dropout_spec, dropout_thr, philox4x32_10, philox_keep_mask, ref_dropout)
+    Dropout, dropout_spec, dropout_thr, philox4x32_10, philox_keep_mask, ref_dropout,
+    ATTN_SITE0, attn_dropout_spec, attn_dropout_thr, philox_attn_keep_mask)
 from .gpt2 import (  # noqa: F401
     _LMHeadXentFn, _LM_CHUNK, _QKV_FUSED, _RES_EPI, _XENT_FUSED, _NT_GELU, _NT_DGELU, _NT_GD, add_layer_norm,
     attention, bias_gelu, cross_entropy, embedding, layer_norm, layer_norm_res, linear_add_layer_norm, lm_head_xent, mlp, mlp_add_layer_norm,
@@ -30,5 +31,5 @@ __all__ = [
     "embedding", "ref_layer_norm", "ref_bias_gelu", "ref_attention",
     "ref_cross_entropy", "use_hip", "linear", "mlp", "qkv_attention", "lm_head_xent",
     "conv_bn_act", "conv_bn_ds_act", "bn_act", "deferred_reductions",
-    "Dropout", "dropout_spec", "philox_keep_mask",
+    "Dropout", "dropout_spec", "philox_keep_mask", "attn_dropout_spec", "philox_attn_keep_mask", "ATTN_SITE0",
 ]

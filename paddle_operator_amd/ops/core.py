@@ -50,16 +50,24 @@ def ref_bias_gelu(x, b):
     return _gelu_tanh(x.float() + b.float()).to(x.dtype)
 
 
-def ref_attention(q, k, v, causal=True):
-    """q,k,v: [B, H, S, D] → [B, H, S, D] (fp32 math)."""
-    qf, kf, vf = q.float(), k.float(), v.float()
-    s = qf @ kf.transpose(-1, -2) / math.sqrt(q.shape[-1])
+def ref_attention(q, k, v, causal=True, keep=None, scale=1.0, math_dtype=torch.float32):
+    """q,k,v: [B, H, S, D] → [B, H, S, D] (fp32 math).
+
+    ``keep`` (bool [B, H, S, S], ``philox_attn_keep_mask``) and ``scale``:
+    attention-probability dropout with an explicit mask — the softmax is taken
+    over the undropped scores, then P ← keep ? P·scale : 0.  Differentiable.
+    ``math_dtype``: the dtype of the two matmuls' operands (the softmax stays
+    fp32); bf16 makes this the framework-bf16 form of the same computation."""
+    qf, kf, vf = q.to(math_dtype), k.to(math_dtype), v.to(math_dtype)
+    s = (qf @ kf.transpose(-1, -2)).float() / math.sqrt(q.shape[-1])
     if causal:
         S = q.shape[-2]
         mask = torch.ones(S, S, dtype=torch.bool, device=q.device).triu(1)
         s = s.masked_fill(mask, float("-inf"))
     p = torch.softmax(s, dim=-1)
-    return (p @ vf).to(q.dtype)
+    if keep is not None:
+        p = torch.where(keep.to(p.device), p * scale, torch.zeros((), dtype=p.dtype, device=p.device))
+    return (p.to(math_dtype) @ vf).to(q.dtype)
 
 
 def ref_cross_entropy(logits, target, vocab: int | None = None):
@@ -167,6 +175,66 @@ def ref_dropout(t: torch.Tensor, drop) -> torch.Tensor:
     """drop(t) with the host-built mask, in t's dtype (differentiable)."""
     keep = philox_keep_mask(t.shape, drop.thr, drop.seed, drop.site, drop.step).to(t.device)
     return torch.where(keep, t * drop.scale, torch.zeros((), dtype=t.dtype, device=t.device))
+
+
+# attention-probability dropout: one Philox call per 4-query × 4-key patch
+
+ATTN_SITE0 = 0x10000  # attention sites are ATTN_SITE0 + layer (0 and 1 + 2i / 2 + 2i are taken)
+
+
+def _attn_patch_words(g, seed: int, site: int, step: int):
+    """The four Philox output words of the attention patches ``g`` (uint64 array
+    of 64-bit patch indices): counter (g_lo, g_hi, site, step), key = seed halves."""
+    import numpy as np
+    g = np.asarray(g, dtype=np.uint64)
+    return philox4x32_10((g & np.uint64(_U32), g >> np.uint64(32), site, step), (seed & _U32, (seed >> 32) & _U32))
+
+
+def philox_attn_keep_mask(B: int, H: int, S: int, thr8: int, seed: int, site: int, step: int,
+                          bh0: int = 0) -> torch.Tensor:
+    """The attention-dropout keep mask as the flash kernels draw it
+    (csrc/hip/philox.h), built on the host: bool [B, H, S, S], True = kept,
+    indexed [b, h, query, key] (entries above the causal diagonal are drawn
+    too; attention never reads them).
+
+    One Philox4x32-10 call serves a patch of 4 queries × 4 keys: counter =
+    (g_lo, g_hi, site, step) with g = ((b·H + h)·P + q//4)·P + k//4 as a 64-bit
+    value, P = S/4 (rounded up when S is no multiple of 4, which only the
+    reference paths see); key = (low, high) half of ``seed``.  Element (q, k)
+    takes output word q % 4, bits 8·(k % 4) … + 7, and is kept iff that byte ≥
+    ``thr8`` = round(p·256): p is quantised to 1/256.  ``bh0`` is added to
+    b·H + h (a slice of a larger batch; the tests reach g ≥ 2^32 with it)."""
+    import numpy as np
+    if not 0 <= thr8 <= 255 or min(B, H, S) < 1:
+        raise ValueError(f"philox_attn_keep_mask: thr8 in [0, 255] and positive sizes required, got {(B, H, S, thr8)}")
+    P = (S + 3) // 4
+    u = np.uint64
+    bh = (np.arange(B * H, dtype=np.uint64) + u(bh0)).reshape(-1, 1, 1)
+    q4 = np.arange(P, dtype=np.uint64).reshape(1, -1, 1)
+    k4 = np.arange(P, dtype=np.uint64).reshape(1, 1, -1)
+    g = (bh * u(P) + q4) * u(P) + k4  # [BH, P, P]
+    w = np.stack(_attn_patch_words(g, seed, site, step), axis=-1)  # [BH, P, P, 4 (q % 4)]
+    byte = (w[..., None] >> (np.arange(4, dtype=np.uint64) * u(8))) & u(0xFF)  # [BH, P, P, q % 4, k % 4]
+    keep = (byte >= u(thr8)).transpose(0, 1, 3, 2, 4).reshape(B * H, 4 * P, 4 * P)[:, :S, :S]
+    return torch.from_numpy(np.ascontiguousarray(keep)).reshape(B, H, S, S)
+
+
+def attn_dropout_thr(p: float) -> int:
+    """round(p·256) clamped to [0, 255]."""
+    return max(0, min(255, int(round(float(p) * 256.0))))
+
+
+def attn_dropout_spec(p: float, seed: int, site: int, step: int):
+    """The ``drop`` argument of ``attention`` / ``qkv_attention`` for probability
+    ``p``: a ``Dropout`` whose ``thr`` is thr8 = round(p·256) (attention dropout
+    is quantised to 1/256) and whose ``scale`` is fp32 256 / (256 − thr8); None
+    when thr8 == 0.  ``site``: ``ATTN_SITE0`` + layer."""
+    import numpy as np
+    thr = attn_dropout_thr(p)
+    if thr == 0:
+        return None
+    scale = float(np.float32(256.0) / np.float32(256 - thr))
+    return Dropout(thr, scale, seed & 0xFFFFFFFFFFFFFFFF, site & _U32, step & _U32)
 
 
 # ----------------------------------------------------------------------------

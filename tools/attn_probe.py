@@ -1,6 +1,11 @@
 """Causal attention microbenchmark (GPT-2-medium shape) — pdo HIP kernels vs torch SDPA.
 
-    python tools/attn_probe.py [--B 32] [--S 1024] [--H 16]
+    python tools/attn_probe.py [--B 32] [--S 1024] [--H 16] [--drop 0.1] [--no-sdpa]
+
+``--drop P`` also times the DROP instantiations (attention-probability dropout inside
+the kernels, csrc/hip/philox.h).  The extension launches dQ and dK/dV as one backward
+call, so the event-timed backward is their sum; the per-kernel split comes from the same
+probe under ``rocprofv3 --kernel-trace --stats`` (recorded in profiles/r8_attn_dropout.md).
 """
 import argparse
 import os
@@ -31,6 +36,8 @@ def main():
     ap.add_argument("--B", type=int, default=32)
     ap.add_argument("--S", type=int, default=1024)
     ap.add_argument("--H", type=int, default=16)
+    ap.add_argument("--drop", type=float, default=0.0, help="also time the kernels with this attention dropout")
+    ap.add_argument("--no-sdpa", action="store_true", help="skip the framework SDPA comparison")
     a = ap.parse_args()
     from paddle_operator_amd import _native
     m = _native.require_hip()
@@ -45,6 +52,17 @@ def main():
     o, lse = m.attn_fwd(qkv.view(B, S, 3 * H * D), H)
     res["pdo_fwd_us"] = bench(lambda: m.attn_fwd(qkv.view(B, S, 3 * H * D), H))
     res["pdo_bwd_us"] = bench(lambda: m.attn_bwd(dout.view(B, S, H * D), qkv.view(B, S, 3 * H * D), o, lse, H))
+    if a.drop > 0.0:
+        from paddle_operator_amd.ops.core import attn_dropout_spec
+        kw = attn_dropout_spec(a.drop, 0x9E3779B97F4A7C15, 0x10000, 1).kw()
+        od, lsed = m.attn_fwd(qkv.view(B, S, 3 * H * D), H, **kw)
+        res["drop_thr8"] = kw["thr"]
+        res["pdo_fwd_drop_us"] = bench(lambda: m.attn_fwd(qkv.view(B, S, 3 * H * D), H, **kw))
+        res["pdo_bwd_drop_us"] = bench(
+            lambda: m.attn_bwd(dout.view(B, S, H * D), qkv.view(B, S, 3 * H * D), od, lsed, H, **kw))
+    if a.no_sdpa:
+        print(json.dumps({k_: (round(v_, 1) if isinstance(v_, float) else v_) for k_, v_ in res.items()}))
+        return
     # correctness vs SDPA (fp32 math on bf16 inputs)
     q, k, v = [qkv[:, :, i].transpose(1, 2) for i in range(3)]
     ref = F.scaled_dot_product_attention(q.float(), k.float(), v.float(), is_causal=True)
