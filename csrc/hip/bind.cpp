@@ -714,6 +714,22 @@ std::vector<at::Tensor> conv_fwd(at::Tensor x, at::Tensor w, int64_t stride, int
 
 int64_t conv_tile_rows(int64_t K) { return pdo::conv_fwd_tile_rows((int)K); }
 
+// The gradient kernels index dy as [N, K, Ho, Wo] computed from the input's
+// (N, H, W) and the convolution's geometry: a dy of any other shape would be read
+// out of range, so it is an error here, before anything is allocated or launched.
+static void check_conv_dy(const char* op, const at::Tensor& dy, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
+                          int64_t R, int64_t S, int64_t stride, int64_t pad) {
+  const int64_t lim = 1 << 24;
+  TORCH_CHECK(N > 0 && N < lim && H > 0 && H < lim && W > 0 && W < lim && C > 0 && C < lim && K > 0 && K < lim &&
+              R > 0 && R < 16 && S > 0 && S < 16 && stride > 0 && stride < 16 && pad >= 0 && pad < 16 &&
+              pdo::conv_supported((int)N, (int)H, (int)W, (int)C, (int)K, (int)R, (int)S, (int)stride, (int)pad),
+              op, ": unsupported convolution N ", N, " H ", H, " W ", W, " C ", C, " K ", K, " R ", R, " S ", S,
+              " stride ", stride, " pad ", pad);
+  const int64_t Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
+  TORCH_CHECK(dy.dim() == 4 && dy.size(0) == N && dy.size(1) == K && dy.size(2) == Ho && dy.size(3) == Wo,
+              op, ": dy must be [", N, ", ", K, ", ", Ho, ", ", Wo, "], got ", dy.sizes());
+}
+
 // Wᵀ of a channels_last [K, C, R, S] weight: [C, R·S·K] (the input-gradient GEMM's B)
 at::Tensor conv_weight_t(at::Tensor w) {
   CHECK_BF16(w);
@@ -742,7 +758,9 @@ at::Tensor conv_dgrad(at::Tensor dy, at::Tensor wt, int64_t C, int64_t R, int64_
   TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 && dy.is_contiguous(at::MemoryFormat::ChannelsLast),
               "conv_dgrad: channels_last bf16 dy");
   const int N = (int)dy.size(0), K = (int)dy.size(1);
-  TORCH_CHECK(wt.is_contiguous() && wt.size(0) == C && wt.size(1) == R * S * K, "conv_dgrad: wt [C, R*S*K]");
+  TORCH_CHECK(wt.is_cuda() && wt.dim() == 2 && wt.is_contiguous() && wt.size(0) == C && wt.size(1) == R * S * K,
+              "conv_dgrad: wt [C, R*S*K]");
+  check_conv_dy("conv_dgrad", dy, N, H, W, C, K, R, S, stride, pad);
   auto dx = at::empty({N, C, H, W}, dy.options(), at::MemoryFormat::ChannelsLast);
   const bf16* ap = nullptr;
   if (add && add->defined()) {
@@ -770,9 +788,12 @@ std::vector<at::Tensor> conv_dgrad_bn(at::Tensor dy, at::Tensor wt, int64_t R, i
   const int N = (int)dy.size(0), K = (int)dy.size(1);
   const int C = (int)bx.size(1), H = (int)bx.size(2), W = (int)bx.size(3);
   TORCH_CHECK(bx.size(0) == N, "conv_dgrad_bn: batch");
-  TORCH_CHECK(wt.is_contiguous() && wt.size(0) == C && wt.size(1) == R * S * K, "conv_dgrad_bn: wt [C, R*S*K]");
+  TORCH_CHECK(wt.is_cuda() && wt.dim() == 2 && wt.is_contiguous() && wt.size(0) == C && wt.size(1) == R * S * K,
+              "conv_dgrad_bn: wt [C, R*S*K]");
   for (const at::Tensor* t : {&mean, &invstd, &w, &b})
-    TORCH_CHECK(t->numel() == C && t->is_contiguous(), "conv_dgrad_bn: per-channel BatchNorm tensors");
+    TORCH_CHECK(t->is_cuda() && t->numel() == C && t->is_contiguous(), "conv_dgrad_bn: per-channel BatchNorm tensors");
+  TORCH_CHECK(bx.is_cuda(), "conv_dgrad_bn: bx on the device");
+  check_conv_dy("conv_dgrad_bn", dy, N, H, W, C, K, R, S, stride, pad);
   auto dx = at::empty({N, C, H, W}, dy.options(), at::MemoryFormat::ChannelsLast);
   auto part = at::empty({pdo::conv_dgrad_tiles(N, H, W, C, (int)R, (int)stride, (int)pad), 2, C},
                         dy.options().dtype(at::kFloat));
@@ -788,8 +809,10 @@ at::Tensor conv_wgrad(at::Tensor dy, at::Tensor x, int64_t R, int64_t S, int64_t
                       c10::optional<at::Tensor> out) {
   CHECK_BF16(dy); CHECK_BF16(x);
   TORCH_CHECK(dy.is_cuda() && dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-              x.is_contiguous(at::MemoryFormat::ChannelsLast), "conv_wgrad: channels_last bf16 dy, x");
+              x.is_cuda() && x.dim() == 4 && dy.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "conv_wgrad: channels_last bf16 dy, x");
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3), K = (int)dy.size(1);
+  check_conv_dy("conv_wgrad", dy, N, H, W, C, K, R, S, stride, pad);
   at::Tensor dw;
   const bool acc = out.has_value() && out->defined();
   if (acc) {
