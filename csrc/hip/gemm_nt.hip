@@ -37,8 +37,13 @@
 //              row group: [groups][2][N] (Σ, Σ(x − x̄)²), gemm_nt_stats_rows
 //              rows each, merged by batchnorm.hip bn_fwd_tiles — a 1×1
 //              convolution's forward without a statistics pass over its output
-// Rounding matches the unfused path bit for bit: the GEMM result is rounded to
-// bf16 before the activation math, as when it made an HBM round trip.
+// Rounding, this kernel (the 8-wave ring): as the unfused path bit for bit — the
+// GEMM result (+ bias for EPI 1 / 5) is rounded to bf16 when it is staged in
+// LDS, and GELU, GELU' or the addend of EPI 4 / 5 / 6 then work on that bf16
+// value, as when it made an HBM round trip (two roundings for EPI 4 / 5 / 6).
+// The 4-wave mainloop (gemm_nt4.hip) applies them to the fp32 product instead:
+// one rounding; only C of EPI 2 / 9 is the same RNE(A·Bᵀ) on both.  Both
+// contracts are pinned bit for bit by tests/test_gemm_nt_exact_gpu.py.
 #include <stdlib.h>
 
 #include "common.h"
