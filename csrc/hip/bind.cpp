@@ -1201,6 +1201,70 @@ void fold_zero(at::Tensor g, at::Tensor h) {
   CHECK_RC(pdo::fold_zero_bf16(bp(g), bp(h), g.numel(), cur_stream()), "fold_zero_bf16");
 }
 
+// acc = (init ? 0 : acc) + f32(g); g = emit ? bf16(acc) : 0 (gradient accumulation, any length)
+void grad_accum_fold(at::Tensor g, at::Tensor acc, bool init, bool emit) {
+  CHECK_IN(g); CHECK_IN(acc); CHECK_BF16(g); CHECK_F32(acc);
+  TORCH_CHECK(g.numel() == acc.numel(), "grad_accum_fold: length mismatch");
+  TORCH_CHECK(g.device() == acc.device(), "grad_accum_fold: g and acc on different devices");
+  CHECK_RC(pdo::grad_accum_fold(bp(g), fp(acc), g.numel(), init, emit, cur_stream()), "grad_accum_fold");
+}
+
+// One micro-batch of token windows (data.hip): tok = the uint16 corpus (n tokens) with
+// draw = (seed, stream, m, rank), or a staged [B, S + 1] buffer with draw = None; a 2-byte
+// integer tensor either way.  Returns (idx, tgt) int64 [B, S]; tokens ≥ vocab are counted
+// into bad (int64 [1]).  starts_out (int64 [B], with a draw) receives the window starts;
+// tok = None writes only those, for a corpus of n tokens that need not exist (returns None).
+py::object token_batch(std::optional<at::Tensor> tok, int64_t n, int64_t B, int64_t S, int64_t vocab,
+                       std::optional<at::Tensor> bad,
+                       std::optional<std::tuple<uint64_t, int64_t, uint64_t, int64_t>> draw,
+                       std::optional<at::Tensor> starts_out) {
+  TORCH_CHECK(B >= 1 && B <= 65535 && S >= 1 && S < (1LL << 30), "token_batch: B in [1, 65535] and S in [1, 2^30) required");
+  TORCH_CHECK(vocab >= 1 && vocab <= 65536, "token_batch: uint16 tokens need 1 <= vocab <= 65536");
+  pdo::DataDraw d;
+  if (draw) {
+    const auto [seed, stream, m, rank] = *draw;
+    TORCH_CHECK(stream == 0 || stream == 1, "token_batch: stream is 0 (training) or 1 (evaluation)");
+    TORCH_CHECK(rank >= 0 && (rank + 1) * B <= (1LL << 32), "token_batch: global row rank*B + j must stay below 2^32");
+    TORCH_CHECK(n >= S + 1, "token_batch: the corpus needs at least S + 1 tokens");
+    d.key0 = (uint32_t)seed;
+    d.key1 = (uint32_t)(seed >> 32);
+    d.stream = (uint32_t)stream;
+    d.step = (uint32_t)m;  // m mod 2^32
+    d.row0 = (uint64_t)rank * (uint64_t)B;
+  } else {
+    TORCH_CHECK(tok.has_value() && !starts_out.has_value(), "token_batch: a staged buffer has no drawn starts");
+    TORCH_CHECK(n == B * (S + 1), "token_batch: a staged buffer holds B*(S+1) tokens");
+  }
+  int64_t* sp = nullptr;
+  if (starts_out) {
+    CHECK_IN(*starts_out); CHECK_I64(*starts_out);
+    TORCH_CHECK(starts_out->numel() == B, "token_batch: starts_out must hold B values");
+    sp = starts_out->data_ptr<int64_t>();
+  }
+  if (!tok) {
+    TORCH_CHECK(sp != nullptr, "token_batch: tok = None needs starts_out");
+    CHECK_RC(pdo::token_batch(nullptr, n, (int)B, (int)S, (int)vocab, nullptr, nullptr, nullptr, &d, sp, cur_stream()),
+             "token_batch");
+    return py::none();
+  }
+  CHECK_IN(*tok);
+  TORCH_CHECK(tok->element_size() == 2 && at::isIntegralType(tok->scalar_type(), false),
+              "token_batch: tok must be a 2-byte integer tensor (uint16 tokens)");
+  TORCH_CHECK(tok->numel() == n, "token_batch: tok holds ", tok->numel(), " tokens, n = ", n);
+  TORCH_CHECK(bad.has_value(), "token_batch: bad (int64 [1]) required");
+  CHECK_IN(*bad); CHECK_I64(*bad);
+  TORCH_CHECK(bad->numel() >= 1 && bad->device() == tok->device(), "token_batch: bad must be an int64 counter on tok's device");
+  TORCH_CHECK(!starts_out || starts_out->device() == tok->device(), "token_batch: starts_out on another device");
+  auto opt = at::TensorOptions().dtype(at::kLong).device(tok->device());
+  auto idx = at::empty({B, S}, opt), tgt = at::empty({B, S}, opt);
+  CHECK_RC(pdo::token_batch(reinterpret_cast<const uint16_t*>(tok->data_ptr()), n, (int)B, (int)S, (int)vocab,
+                            idx.data_ptr<int64_t>(), tgt.data_ptr<int64_t>(),
+                            reinterpret_cast<unsigned long long*>(bad->data_ptr<int64_t>()), draw ? &d : nullptr, sp,
+                            cur_stream()),
+           "token_batch");
+  return py::make_tuple(idx, tgt);
+}
+
 // flat[off_i : off_i + n_i] = scale * t_i for every tensor (one launch);
 // reverse: t_i = flat[off_i : off_i + n_i].  bf16 or f32, all one dtype.
 void flatten_scale(std::vector<at::Tensor> ts, at::Tensor flat, std::vector<int64_t> offsets, double scale,
@@ -1436,6 +1500,9 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.def("scale_", &scale_);
   m.def("scale_dev_", &scale_dev_);
   m.def("fold_zero", &fold_zero);
+  m.def("grad_accum_fold", &grad_accum_fold, py::arg("g"), py::arg("acc"), py::arg("init"), py::arg("emit"));
+  m.def("token_batch", &token_batch, py::arg("tok"), py::arg("n"), py::arg("B"), py::arg("S"), py::arg("vocab"),
+        py::arg("bad") = py::none(), py::arg("draw") = py::none(), py::arg("starts_out") = py::none());
   m.def("flatten_scale", &flatten_scale);
   m.def("cast_scale_bf16_f32", &cast_scale_bf16_f32);
   m.def("cast_f32_bf16", &cast_f32_bf16);

@@ -104,6 +104,42 @@ __global__ __launch_bounds__(256) void axpy_dev_kernel(bf16* __restrict__ y, con
   }
 }
 
+// Gradient accumulation over micro-batches in fp32 (train.py GPT2Trainer, grad_accum > 2):
+// acc = (init ? 0 : acc) + f32(g), then g = emit ? bf16(acc) : 0.  One fp32 add and,
+// with emit, one round-to-nearest-even cast per element.  16 B of bf16 per lane;
+// the n % 8 tail elements go one per lane of the first workgroup.
+__global__ __launch_bounds__(256) void grad_accum_fold_kernel(bf16* __restrict__ g, float* __restrict__ acc,
+                                                              long long n, int init, int emit) {
+  const long long nvec = n / 8;
+  const f32x8 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
+    bf16x8* pg = reinterpret_cast<bf16x8*>(g) + i;
+    f32x4* pa = reinterpret_cast<f32x4*>(acc) + 2 * i;
+    f32x8 a = z;
+    if (!init) {
+      const f32x4 lo = pa[0], hi = pa[1];
+      a = f32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    }
+    a += to_f32(*pg);
+    pa[0] = f32x4{a[0], a[1], a[2], a[3]};
+    pa[1] = f32x4{a[4], a[5], a[6], a[7]};
+    *pg = to_bf16(emit ? a : z);
+  }
+  const long long k = nvec * 8 + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < 8 && k < n) {
+    const float a = (init ? 0.f : acc[k]) + (float)g[k];
+    acc[k] = a;
+    g[k] = (bf16)(emit ? a : 0.f);
+  }
+}
+
+int grad_accum_fold(bf16* g, float* acc, long long n, int init, int emit, hipStream_t st) {
+  if (n < 0 || ((uintptr_t)g & 15) || ((uintptr_t)acc & 15)) return -2;
+  if (n == 0) return 0;
+  grad_accum_fold_kernel<<<stream_grid(n / 8, 256), 256, 0, st>>>(g, acc, n, init, emit);
+  return 0;
+}
+
 int axpy_dev_bf16(bf16* y, const bf16* x, long long n, const float* s, hipStream_t st) {
   if (n % 8) return -2;
   if (n == 0) return 0;

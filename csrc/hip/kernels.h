@@ -263,5 +263,22 @@ int scale_dev_bf16(bf16* x, long long n, const float* s, hipStream_t st);
 // y = bf16(y + s·x) with the fp32 scale read on device
 int axpy_dev_bf16(bf16* y, const bf16* x, long long n, const float* s, hipStream_t st);
 int fold_zero_bf16(bf16* g, bf16* h, long long n, hipStream_t st);
+// acc = (init ? 0 : acc) + f32(g); g = emit ? bf16(acc) : 0 (any n; g and acc 16-B aligned)
+int grad_accum_fold(bf16* g, float* acc, long long n, int init, int emit, hipStream_t st);
+
+// data.hip: one micro-batch of token windows from a uint16 corpus, widened to int64.
+// DataDraw travels by value like DropArgs: seed words, stream (0 train, 1 evaluation),
+// the micro-batch counter m mod 2^32 and row0 = rank·B (global row g = row0 + j < 2^32).
+struct DataDraw {
+  uint32_t key0 = 0, key1 = 0;
+  uint32_t stream = 0, step = 0;
+  uint64_t row0 = 0;
+};
+// draw set: tok is the corpus of n tokens (device), row j starts at the drawn start;
+// draw == nullptr: tok is a staged [B][S + 1] buffer (n = B·(S + 1)).
+// tokens ≥ vocab (≤ 65536): idx 0, tgt −1, *bad += 1.  starts_out (optional, with a
+// draw) receives the B starts; tok == nullptr writes only the starts.
+int token_batch(const uint16_t* tok, long long n, int B, int S, int vocab, int64_t* idx, int64_t* tgt,
+                unsigned long long* bad, const DataDraw* draw, int64_t* starts_out, hipStream_t st);
 
 }  // namespace pdo

@@ -45,6 +45,27 @@ def parse_args(argv=None):
                     help="gpt2: attention-probability dropout inside the flash-attention kernels (quantised to 1/256; "
                          "default 0)")
     ap.add_argument("--dropout-seed", type=int, default=0, help="gpt2: seed of the dropout masks")
+    ap.add_argument("--data", default=os.environ.get("PDO_TRAIN_DATA", ""),
+                    help="gpt2: training token file, raw little-endian uint16 ids (nanoGPT train.bin); default: "
+                         "synthetic batches")
+    ap.add_argument("--val-data", default=os.environ.get("PDO_VAL_DATA", ""),
+                    help="gpt2: held-out token file of the same format (--eval-every)")
+    ap.add_argument("--data-seed", type=int, default=0, help="gpt2: 64-bit seed of the window sampler")
+    ap.add_argument("--data-device-gb", type=float, default=8.0,
+                    help="gpt2: a token file up to this size is held in GPU memory; a larger one is read from the "
+                         "host one micro-batch ahead")
+    ap.add_argument("--grad-accum", type=int, default=None,
+                    help="gpt2: micro-batches per optimizer step (default 1); --steps counts optimizer steps")
+    ap.add_argument("--lr", type=float, default=3e-4, help="gpt2: peak learning rate")
+    ap.add_argument("--lr-schedule", choices=["constant", "cosine"], default=None,
+                    help="gpt2: constant (default) or linear warmup + cosine decay")
+    ap.add_argument("--lr-warmup", type=int, default=0, help="gpt2: warmup optimizer steps of --lr-schedule cosine")
+    ap.add_argument("--lr-decay-steps", type=int, default=0,
+                    help="gpt2: optimizer step at which the cosine reaches its floor (default --steps)")
+    ap.add_argument("--lr-min-ratio", type=float, default=0.1, help="gpt2: floor of the cosine as a fraction of --lr")
+    ap.add_argument("--eval-every", type=int, default=0,
+                    help="gpt2: held-out loss on --val-data every N optimizer steps (PDO_EVAL records)")
+    ap.add_argument("--eval-batches", type=int, default=8, help="gpt2: micro-batches per rank of one evaluation")
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="resnet50: keep the step eager (default on one GPU rank: captured once into a HIP graph "
                          "and replayed, workloads/resnet.py; multi-rank steps stay eager)")
@@ -63,7 +84,10 @@ def parse_args(argv=None):
     ap.add_argument("--exit-after-ready", action="store_true")
     ap.add_argument("--timeout", type=int, default=300)
     ap.add_argument("--throttle-ms", type=float, default=0.0, help=argparse.SUPPRESS)  # tests: stretch steps
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.eval_every and not args.val_data:
+        ap.error("--eval-every needs --val-data (or PDO_VAL_DATA)")
+    return args
 
 
 def log(msg: str):
@@ -100,7 +124,12 @@ def run_collective(args, jenv) -> int:
         cfg.embd_pdrop = cfg.resid_pdrop = args.dropout
         cfg.attn_pdrop = args.attn_dropout
         seq = min(args.seq, cfg.n_positions)
-        trainer = GPT2Trainer(cfg, args.batch or (2 if args.tiny else 32), seq, dev, dropout_seed=args.dropout_seed)
+        trainer = GPT2Trainer(cfg, args.batch or (2 if args.tiny else 32), seq, dev, lr=args.lr,
+                              dropout_seed=args.dropout_seed, grad_accum=args.grad_accum or 1,
+                              data=args.data or None, val_data=args.val_data or None, data_seed=args.data_seed,
+                              data_device_gb=args.data_device_gb, lr_schedule=args.lr_schedule or "constant",
+                              lr_warmup=args.lr_warmup, lr_decay_steps=args.lr_decay_steps or args.steps,
+                              lr_min_ratio=args.lr_min_ratio)
         trainer.sync_initial_weights()
         tokens_per_step = trainer.tokens_per_step()
     elif args.workload == "resnet50":
@@ -139,6 +168,9 @@ def run_collective(args, jenv) -> int:
     t0 = time.perf_counter()
     last = t0
     done = 0
+    gpt2 = args.workload == "gpt2"
+    evaluating = gpt2 and args.eval_every > 0 and bool(args.val_data)
+    val_loss = None
     while step < args.steps:
         in_step[0] = True
         with trace.range(f"step {step}"):
@@ -153,9 +185,16 @@ def run_collective(args, jenv) -> int:
         if args.ckpt_dir and args.ckpt_every and step % args.ckpt_every == 0 and b.rank == 0:
             with trace.range("checkpoint"):
                 ckpt.save(state(), args.ckpt_dir, step)
+        if evaluating and step % args.eval_every == 0:
+            with trace.range("evaluate"):
+                val_loss = trainer.evaluate(args.eval_batches)  # every rank: one all-reduce inside
+            if b.rank == 0:
+                print("PDO_EVAL " + json.dumps({"step": step, "val_loss": val_loss}), flush=True)
         if step % args.log_every == 0 or step == args.steps:
             if dev.type == "cuda":
                 torch.cuda.synchronize(dev)
+            if gpt2:
+                trainer.check_data()
             now = time.perf_counter()
             rate = tokens_per_step * b.world * args.log_every / max(now - last, 1e-9)
             last = now
@@ -165,6 +204,9 @@ def run_collective(args, jenv) -> int:
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
+    if gpt2:
+        trainer.check_data()
+        trainer.close()
     if args.ckpt_dir and b.rank == 0:
         ckpt.save(state(), args.ckpt_dir, step)
     summary = {"rank": b.rank, "world": b.world, "steps": done, "seconds": dt,
@@ -173,11 +215,27 @@ def run_collective(args, jenv) -> int:
     if args.workload == "gpt2":
         summary["dropout"] = args.dropout
         summary["attn_dropout"] = args.attn_dropout
+        summary.update(_gpt2_flags(args))
+        if val_loss is not None:
+            summary["val_loss"] = val_loss
     print("PDO_DONE " + json.dumps(summary), flush=True)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+def _gpt2_flags(args) -> dict:
+    """The token-data / accumulation / schedule flags that were given, for the
+    PDO_DONE and PDO_BENCH records (absent keys: the flag was not given)."""
+    out = {}
+    if args.data:
+        out["data"] = args.data
+    if args.grad_accum is not None:
+        out["grad_accum"] = args.grad_accum
+    if args.lr_schedule is not None:
+        out["lr_schedule"] = args.lr_schedule
+    return out
 
 
 def _bench(args, b, jenv, trainer, tokens_per_step, ready_rec) -> int:
@@ -208,6 +266,8 @@ def _bench(args, b, jenv, trainer, tokens_per_step, ready_rec) -> int:
         loss = trainer.step()
     fence()
     dt = time.perf_counter() - t0
+    if args.workload == "gpt2":
+        trainer.check_data()  # after the timed region: reads a device counter
     if args.dump_outputs and loss is not None:
         _dump_outputs(args.dump_outputs, b, trainer, loss)
     res = {"rank": b.rank, "world": b.world, "steps": args.steps, "warmup": args.warmup, "seconds": dt,
@@ -221,6 +281,7 @@ def _bench(args, b, jenv, trainer, tokens_per_step, ready_rec) -> int:
     if args.workload == "gpt2":
         res["dropout"] = args.dropout  # 0.0: the headline is a dropout-free step
         res["attn_dropout"] = args.attn_dropout
+        res.update(_gpt2_flags(args))
     if dev.type == "cuda":
         res["gpu_name"] = torch.cuda.get_device_name(dev)
         res["max_mem_gb"] = round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)
