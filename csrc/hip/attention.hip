@@ -38,14 +38,10 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "cdna4.h"
 #include "kernels.h"
 
 namespace pdo {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
 constexpr int HD = 64;     // head dim
 constexpr int TROWS = 64;  // rows per LDS tile
@@ -55,24 +51,6 @@ constexpr float LN2 = 0.6931471805599453f;
 __device__ __forceinline__ int swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
 // element offset of (row r, 16-B chunk ch) in a swizzled [64][64] bf16 tile
 __device__ __forceinline__ int toff(int r, int ch) { return r * HD + ((ch ^ swz(r)) << 3); }
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-
-__device__ __forceinline__ f32x16 bcast16(float v) {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = v;
-  return z;
-}
 
 // operand prescale: x ← bf16(c · x), once per workgroup on the register-resident
 // operand, so every score MFMA yields c2·q·k directly (log2-domain logits) and
@@ -95,16 +73,10 @@ __device__ __forceinline__ bf16x8 tr_frag(const bf16* T, int k0, int cbase, int 
   const int col = cbase + 16 * (g & 1) + 4 * p;
   const int r0 = k0 + 4 * (g >> 1) + q;
   const int ch = col >> 3, in = col & 7;
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(T + toff(r0, ch) + in));
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(T + toff(r0 + 8, ch) + in));
-  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-// transposed fragment from two precomputed per-lane addresses (rows k0 and k0 + 8)
-__device__ __forceinline__ bf16x8 ld_tr(const bf16* lo_p, const bf16* hi_p) {
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)lo_p);
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)hi_p);
-  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  // not ld_tr8: each address is formed next to its read (the backward kernels' schedule depends on it)
+  const bf16x4 lo = ld_tr4(T + toff(r0, ch) + in);
+  const bf16x4 hi = ld_tr4(T + toff(r0 + 8, ch) + in);
+  return cat8(lo, hi);
 }
 
 // 8 accumulator registers [8s, 8s+8) → bf16 B-operand fragment
@@ -191,24 +163,13 @@ __device__ __forceinline__ void stage_store(const Stage& st, bf16* T, int tid) {
 // The XOR swizzle is applied on the SOURCE side: the lane fetches logical chunk
 // (l & 7) ^ swz(row), which toff() places at chunk l & 7.  Wave w moves pieces
 // 2w and 2w + 1 of every tile; swz() only sees row bits 1-3, so the per-lane
-// byte offsets of an even and an odd piece are two loop-invariant VGPRs.  M0
-// carries the piece's LDS address (nothing else in these kernels reads M0);
-// s_nop 0 = the SALU M0 write → LDS-DMA wait state.  The DMA counts in vmcnt:
-// consumers wait with s_waitcnt vmcnt(N) for their own pieces, then barrier.
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
+// byte offsets of an even and an odd piece are two loop-invariant VGPRs.  The
+// pieces go out with glds16 / glds4 (cdna4.h), which leave M0 changed: nothing
+// else in these kernels reads M0.  Consumers wait with vm_wait<N>() for their
+// own pieces, then barrier.
 __device__ __forceinline__ unsigned dma_voff(int lane, size_t row_stride, int odd) {
   const int rr = lane >> 3;
   return (unsigned)(((size_t)rr * row_stride + (size_t)(((lane & 7) ^ swz(8 * odd + rr)) << 3)) * 2);
-}
-__device__ __forceinline__ void glds16(unsigned voff, const void* sbase, unsigned lds_byte) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_byte)
-               : "memory");
-}
-__device__ __forceinline__ void glds4(unsigned voff, const void* sbase, unsigned lds_byte) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_byte)
-               : "memory");
 }
 // rows [row0 + 16w, row0 + 16w + 16) of a [rows][64] bf16 matrix → the wave's 2 pieces of an LDS tile
 __device__ __forceinline__ void dma_tile(const bf16* base, size_t row_stride, int row0, int wu, unsigned v_even,
@@ -216,10 +177,6 @@ __device__ __forceinline__ void dma_tile(const bf16* base, size_t row_stride, in
   const bf16* src = base + (size_t)(row0 + 16 * wu) * row_stride;
   glds16(v_even, src, lds_tile + 2048 * wu);
   glds16(v_odd, src + 8 * row_stride, lds_tile + 2048 * wu + 1024);
-}
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // store a 32x32 f32 accumulator (lane col = row index `rowv`, regs = 32 columns
@@ -311,9 +268,7 @@ __device__ __forceinline__ int tr_base_v(int cbase, int lane) {
 
 template <int K0>
 __device__ __forceinline__ bf16x8 tr_frag_v(const bf16* Tlane) {
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(Tlane + K0 * HD));
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(Tlane + (K0 + 8) * HD));
-  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return ld_tr8(Tlane + K0 * HD, Tlane + (K0 + 8) * HD);
 }
 
 // causal triangle of a 32x32 block whose first key and first query coincide:
@@ -351,7 +306,6 @@ __device__ __forceinline__ void store_acc_rows_pk(bf16* dst_row, const f32x16& a
   }
 }
 
-typedef bf16 bf16x2 __attribute__((ext_vector_type(2)));
 // l += Σ of the 8 bf16 P values of a B-operand fragment (the values P·V uses)
 __device__ __forceinline__ float rowsum8(bf16x8 p, float acc) {
   const bf16x2 one = {(bf16)1.f, (bf16)1.f};
@@ -459,8 +413,9 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
   __amdgpu_buffer_rsrc_t rk, rv;
   if constexpr (NEW) {
     const int nbytes = (int)((size_t)S * rs * 2 - (size_t)H * HD * 2 * 2 - (size_t)h * HD * 2);
-    rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(kbase), 0, nbytes, 0x00020000);
-    rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(vbase), 0, nbytes, 0x00020000);
+    // the builtin, not buf_rsrc: through the helper hipcc orders this kernel's scalar prologue differently
+    rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(kbase), 0, nbytes, BUF_RAW32);
+    rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(vbase), 0, nbytes, BUF_RAW32);
     stage_voff(vo, rs, tid);
     stage_load_buf(sk, rk, vo, 0);
     stage_load_buf(sv, rv, vo, 0);
@@ -491,8 +446,8 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
       f32x16 s0 = nm16, s1 = nm16;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        s0 = mfma(row_frag(Kt, 0, ks, lane), qf[ks], s0);
-        s1 = mfma(row_frag(Kt, 32, ks, lane), qf[ks], s1);
+        s0 = mfma32(row_frag(Kt, 0, ks, lane), qf[ks], s0);
+        s1 = mfma32(row_frag(Kt, 32, ks, lane), qf[ks], s1);
       }
       if (key0 + TROWS - 1 > qb * 128 + w * 32) {  // diagonal tile (wave-uniform)
         if constexpr (NEW) {
@@ -589,10 +544,10 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
           p0 = drop8_q(p0, t0.t[0], t0.t[1]);
           p1 = drop8_q(p1, t1.t[0], t1.t[1]);
         }
-        o0 = mfma(tr_frag_v<0>(V0), p0, o0);
-        o1 = mfma(tr_frag_v<0>(V1), p0, o1);
-        o0 = mfma(tr_frag_v<32>(V0), p1, o0);
-        o1 = mfma(tr_frag_v<32>(V1), p1, o1);
+        o0 = mfma32(tr_frag_v<0>(V0), p0, o0);
+        o1 = mfma32(tr_frag_v<0>(V1), p0, o1);
+        o0 = mfma32(tr_frag_v<32>(V0), p1, o0);
+        o1 = mfma32(tr_frag_v<32>(V1), p1, o1);
       }
       {
         bf16x8 p0 = pack8(s0, 1), p1 = pack8(s1, 1);
@@ -604,10 +559,10 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
           p0 = drop8_q(p0, t0.t[2], t0.t[3]);
           p1 = drop8_q(p1, t1.t[2], t1.t[3]);
         }
-        o0 = mfma(tr_frag_v<16>(V0), p0, o0);
-        o1 = mfma(tr_frag_v<16>(V1), p0, o1);
-        o0 = mfma(tr_frag_v<48>(V0), p1, o0);
-        o1 = mfma(tr_frag_v<48>(V1), p1, o1);
+        o0 = mfma32(tr_frag_v<16>(V0), p0, o0);
+        o1 = mfma32(tr_frag_v<16>(V1), p0, o1);
+        o0 = mfma32(tr_frag_v<48>(V0), p1, o0);
+        o1 = mfma32(tr_frag_v<48>(V1), p1, o1);
       }
       if constexpr (DOT) l += la + lb;
     }
@@ -770,23 +725,23 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
           // two k-steps of fragments in flight (16 VGPRs)
           bf16x8 qa0 = row_frag(Qt, 32 * qs, 0, lane), da0 = row_frag(Dt, 32 * qs, 0, lane);
           bf16x8 qa1 = row_frag(Qt, 32 * qs, 1, lane), da1 = row_frag(Dt, 32 * qs, 1, lane);
-          sacc = mfma(qa0, kf[0], sacc);
-          dpacc = mfma(da0, vf[0], dpacc);
+          sacc = mfma32(qa0, kf[0], sacc);
+          dpacc = mfma32(da0, vf[0], dpacc);
           qa0 = row_frag(Qt, 32 * qs, 2, lane);
           da0 = row_frag(Dt, 32 * qs, 2, lane);
-          sacc = mfma(qa1, kf[1], sacc);
-          dpacc = mfma(da1, vf[1], dpacc);
+          sacc = mfma32(qa1, kf[1], sacc);
+          dpacc = mfma32(da1, vf[1], dpacc);
           qa1 = row_frag(Qt, 32 * qs, 3, lane);
           da1 = row_frag(Dt, 32 * qs, 3, lane);
-          sacc = mfma(qa0, kf[2], sacc);
-          dpacc = mfma(da0, vf[2], dpacc);
-          sacc = mfma(qa1, kf[3], sacc);
-          dpacc = mfma(da1, vf[3], dpacc);
+          sacc = mfma32(qa0, kf[2], sacc);
+          dpacc = mfma32(da0, vf[2], dpacc);
+          sacc = mfma32(qa1, kf[3], sacc);
+          dpacc = mfma32(da1, vf[3], dpacc);
         } else {
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) {
-            sacc = mfma(row_frag(Qt, 32 * qs, ks, lane), kf[ks], sacc);
-            dpacc = mfma(row_frag(Dt, 32 * qs, ks, lane), vf[ks], dpacc);
+            sacc = mfma32(row_frag(Qt, 32 * qs, ks, lane), kf[ks], sacc);
+            dpacc = mfma32(row_frag(Dt, 32 * qs, ks, lane), vf[ks], dpacc);
           }
         }
         // The causal mask only touches the diagonal sub-tile (wave-uniform): a
@@ -831,17 +786,17 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
             const bf16x8 t2 = tr_frag(Qt, 32 * qs + 16 * sst, 0, lane), t3 = tr_frag(Qt, 32 * qs + 16 * sst, 32, lane);
             const bf16x8 pb = pack8(sacc, sst);
             const bf16x8 db = pack8(dpacc, sst);
-            dv0 = mfma(t0, pb, dv0);
-            dv1 = mfma(t1, pb, dv1);
-            dk0 = mfma(t2, db, dk0);
-            dk1 = mfma(t3, db, dk1);
+            dv0 = mfma32(t0, pb, dv0);
+            dv1 = mfma32(t1, pb, dv1);
+            dk0 = mfma32(t2, db, dk0);
+            dk1 = mfma32(t3, db, dk1);
           } else {
             const bf16x8 pb = pack8(sacc, sst);
             const bf16x8 db = pack8(dpacc, sst);
-            dv0 = mfma(tr_frag(Dt, 32 * qs + 16 * sst, 0, lane), pb, dv0);
-            dv1 = mfma(tr_frag(Dt, 32 * qs + 16 * sst, 32, lane), pb, dv1);
-            dk0 = mfma(tr_frag(Qt, 32 * qs + 16 * sst, 0, lane), db, dk0);
-            dk1 = mfma(tr_frag(Qt, 32 * qs + 16 * sst, 32, lane), db, dk1);
+            dv0 = mfma32(tr_frag(Dt, 32 * qs + 16 * sst, 0, lane), pb, dv0);
+            dv1 = mfma32(tr_frag(Dt, 32 * qs + 16 * sst, 32, lane), pb, dv1);
+            dk0 = mfma32(tr_frag(Qt, 32 * qs + 16 * sst, 0, lane), db, dk0);
+            dk1 = mfma32(tr_frag(Qt, 32 * qs + 16 * sst, 32, lane), db, dk1);
           }
         }
       }
@@ -968,8 +923,8 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
   int roff[4], tlo[2], thi[2];
   if constexpr (NEW) {
     const int nbytes = (int)((size_t)S * rs * 2 - (size_t)H * HD * 2 * 2 - (size_t)h * HD * 2);
-    rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(kbase), 0, nbytes, 0x00020000);
-    rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(vbase), 0, nbytes, 0x00020000);
+    rk = buf_rsrc(kbase, nbytes);
+    rv = buf_rsrc(vbase, nbytes);
     stage_voff(vo, rs, tid);
     stage_load_buf(sk, rk, vo, 0);
     stage_load_buf(sv, rv, vo, 0);
@@ -1014,11 +969,11 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
           if constexpr (NEW) {
-            s = mfma(*reinterpret_cast<const bf16x8*>(Kt + 32 * ksub * HD + roff[ks]), qf[ks], s);
-            dp = mfma(*reinterpret_cast<const bf16x8*>(Vt + 32 * ksub * HD + roff[ks]), df[ks], dp);
+            s = mfma32(*reinterpret_cast<const bf16x8*>(Kt + 32 * ksub * HD + roff[ks]), qf[ks], s);
+            dp = mfma32(*reinterpret_cast<const bf16x8*>(Vt + 32 * ksub * HD + roff[ks]), df[ks], dp);
           } else {
-            s = mfma(row_frag(Kt, 32 * ksub, ks, lane), qf[ks], s);
-            dp = mfma(row_frag(Vt, 32 * ksub, ks, lane), df[ks], dp);
+            s = mfma32(row_frag(Kt, 32 * ksub, ks, lane), qf[ks], s);
+            dp = mfma32(row_frag(Vt, 32 * ksub, ks, lane), df[ks], dp);
           }
         }
         KeepBits<DROP> tk;
@@ -1052,11 +1007,11 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
           const bf16x8 dsb = pack8(s, sst);
           if constexpr (NEW) {
             const bf16* T = Kt + (32 * ksub + 16 * sst) * HD;
-            a0 = mfma(ld_tr(T + tlo[0], T + thi[0]), dsb, a0);
-            a1 = mfma(ld_tr(T + tlo[1], T + thi[1]), dsb, a1);
+            a0 = mfma32(ld_tr8(T + tlo[0], T + thi[0]), dsb, a0);
+            a1 = mfma32(ld_tr8(T + tlo[1], T + thi[1]), dsb, a1);
           } else {
-            a0 = mfma(tr_frag(Kt, 32 * ksub + 16 * sst, 0, lane), dsb, a0);
-            a1 = mfma(tr_frag(Kt, 32 * ksub + 16 * sst, 32, lane), dsb, a1);
+            a0 = mfma32(tr_frag(Kt, 32 * ksub + 16 * sst, 0, lane), dsb, a0);
+            a1 = mfma32(tr_frag(Kt, 32 * ksub + 16 * sst, 32, lane), dsb, a1);
           }
         }
       }

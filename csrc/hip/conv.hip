@@ -45,7 +45,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "cdna4.h"
 #include "kernels.h"
 
 namespace pdo {
@@ -54,16 +54,6 @@ namespace {
 
 constexpr int CNT = 256;
 constexpr unsigned OOB = 0x80000000u;  // ≥ any buffer's num_records: the load returns zeros
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_t;
-
-template <typename Fn, int... I>
-__device__ __forceinline__ void static_for_impl(Fn&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename Fn>
-__device__ __forceinline__ void static_for(Fn&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 struct ConvArgs {
   const bf16* x;         // A source, NHWC [N][IH][IW][C]
@@ -91,29 +81,8 @@ struct ConvArgs {
   int dh[9], dw[9], bcol[9];
 };
 
-// q = x / d, r = x - q·d for 0 ≤ x < 2^24 (exact via a float reciprocal + one correction)
-__device__ __forceinline__ void divmod(int x, int d, float inv, int& q, int& r) {
-  q = (int)((float)x * inv);
-  r = x - q * d;
-  if (r < 0) {
-    --q;
-    r += d;
-  } else if (r >= d) {
-    ++q;
-    r -= d;
-  }
-}
-
-__device__ __forceinline__ void bufld(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned lds_byte) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs),
-               "s"(lds_byte)
-               : "memory");
-}
-__device__ __forceinline__ void glds(unsigned voff, const void* sbase, unsigned lds_byte) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase),
-               "s"(lds_byte)
-               : "memory");
-}
+// Every kernel here stages through bufld16_lds / glds16, the LDS-DMA forms that
+// leave M0 changed: the DMAs are the only M0 users in these kernels.
 
 // Epilogue shared by the implicit-GEMM mainloops: acc[i][j][e] =
 // C[m = wm·RW + 16i + 4(l >> 4) + e][col n0 + wn·64 + 4(l & 15) + j] (RW = BM / WM
@@ -260,11 +229,7 @@ __global__ __launch_bounds__(CNT, 2) void conv_igemm_kernel(const ConvArgs a) {
   const long long ntm = (a.M + BM - 1) / BM;
   // bijective XCD remap: blocks b and b + 8 share an XCD, so each XCD walks a
   // contiguous range of tiles — the ntn tiles of one token range share its L2
-  long long id = blockIdx.x;
-  {
-    const long long nwg = ntm * ntn, q = nwg >> 3, r = nwg & 7, x = id & 7, slot = id >> 3;
-    id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + slot;
-  }
+  const long long id = xcd_remap((long long)blockIdx.x, ntm * ntn);
   const int tn = (int)(id % ntn);
   const long long tm = id / ntn;
   const long long m0 = tm * BM;
@@ -303,8 +268,8 @@ __global__ __launch_bounds__(CNT, 2) void conv_igemm_kernel(const ConvArgs a) {
     const int cg = (lane & 7) ^ ((pr >> 1) & 7);
     voffB[i] = (unsigned)((col * a.ldb + cg * 8) * 2);
   }
-  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.x), 0, (int)a.xbytes, 0x00020000);
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const __amdgpu_buffer_rsrc_t rsX = buf_rsrc(a.x, (int)a.xbytes);
+  const unsigned lds0 = lds_addr(smem);
   const int CC = a.C >= 64 ? a.C >> 6 : 1;  // C = 16: one k-step per tap (a row of 4 pixels)
   const int nk = a.ntaps * CC;
 
@@ -318,11 +283,11 @@ __global__ __launch_bounds__(CNT, 2) void conv_igemm_kernel(const ConvArgs a) {
       const int hi = hb[i] + dh, wi = wb[i] + dw;
       const bool ok = (unsigned)hi < (unsigned)a.IH && (unsigned)wi < (unsigned)a.IW;
       const unsigned v = ok ? (unsigned)((base[i] + coff) * 2) : OOB;
-      bufld(v, rsX, sb + (unsigned)((w + 4 * i) * 1024));
+      bufld16_lds(v, rsX, sb + (unsigned)((w + 4 * i) * 1024));
     }
     const bf16* bsrc = a.w + a.bcol[tap] + cc * 64;
 #pragma unroll
-    for (int i = 0; i < NB; ++i) glds(voffB[i], bsrc, sb + (unsigned)(BM * 128 + (w + 4 * i) * 1024));
+    for (int i = 0; i < NB; ++i) glds16(voffB[i], bsrc, sb + (unsigned)(BM * 128 + (w + 4 * i) * 1024));
   };
 
   // ---- fragment offsets (bytes within a stage)
@@ -340,9 +305,9 @@ __global__ __launch_bounds__(CNT, 2) void conv_igemm_kernel(const ConvArgs a) {
   for (int kt = 0; kt < nk; ++kt) {
     if (kt + 1 < nk) {
       issue(kt + 1, (kt + 1) & 1);
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NA + NB) : "memory");  // k-step kt landed (kt + 1 flies)
+      vm_wait<NA + NB>();  // k-step kt landed (kt + 1 flies)
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      vm_wait<0>();
     }
     __builtin_amdgcn_s_barrier();  // ... for every wave's pieces
     const char* st = smem + (kt & 1) * STAGE;
@@ -439,9 +404,9 @@ __global__ __launch_bounds__(CNT, 2) void conv_wgrad_kernel(const WgradArgs a) {
   const int kq = a.ksteps / a.splits, kr = a.ksteps % a.splits;
   const int k0 = split * kq + min(split, kr), nk = kq + (split < kr ? 1 : 0);
 
-  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.dy), 0, (int)a.dybytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.x), 0, (int)a.xbytes, 0x00020000);
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const __amdgpu_buffer_rsrc_t rsY = buf_rsrc(a.dy, (int)a.dybytes);
+  const __amdgpu_buffer_rsrc_t rsX = buf_rsrc(a.x, (int)a.xbytes);
+  const unsigned lds0 = lds_addr(smem);
   // per-lane constant parts of the pieces: row in the tile, source chunk
   auto issue = [&](int kt, int stage) {
     const long long t0 = (long long)kt * 64;
@@ -453,7 +418,7 @@ __global__ __launch_bounds__(CNT, 2) void conv_wgrad_kernel(const WgradArgs a) {
       const int c = (lane % LA) ^ wswz<RA>(row);
       const long long t = t0 + row;
       const unsigned v = t < a.M ? (unsigned)((t * a.Kout + co0 + c * 8) * 2) : OOB;
-      bufld(v, rsY, sb + (unsigned)(p * 1024));
+      bufld16_lds(v, rsY, sb + (unsigned)(p * 1024));
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
@@ -470,7 +435,7 @@ __global__ __launch_bounds__(CNT, 2) void conv_wgrad_kernel(const WgradArgs a) {
         if ((unsigned)hi < (unsigned)a.IH && (unsigned)wi < (unsigned)a.IW)
           v = (unsigned)(((((long long)n * a.IH + hi) * a.IW + wi) * a.C + ci0 + c * 8) * 2);
       }
-      bufld(v, rsX, sb + (unsigned)(SA + p * 1024));
+      bufld16_lds(v, rsX, sb + (unsigned)(SA + p * 1024));
     }
   };
   // transposed fragment of the 16 columns cb..cb+15, tokens 32kk + {4g..4g+3, 16+4g..}
@@ -481,9 +446,7 @@ __global__ __launch_bounds__(CNT, 2) void conv_wgrad_kernel(const WgradArgs a) {
     const int r0 = 32 * kk + 4 * g + q4, r1 = r0 + 16;
     const char* a0 = T + r0 * RW + (((col >> 3) ^ wswz<RW>(r0)) << 4) + (col & 7) * 2;
     const char* a1 = T + r1 * RW + (((col >> 3) ^ wswz<RW>(r1)) << 4) + (col & 7) * 2;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)a0);
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)a1);
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return ld_tr8(a0, a1);
   };
   using IRA = std::integral_constant<int, RA>;
   using IRB = std::integral_constant<int, RB>;
@@ -503,10 +466,10 @@ __global__ __launch_bounds__(CNT, 2) void conv_wgrad_kernel(const WgradArgs a) {
     if (k + NS - 1 < nk) issue(k0 + k + NS - 1, (k + NS - 1) % NS);
     // steps issued after k (in flight behind it): min(NS - 1, nk - 1 - k)
     const int after = nk - 1 - k < NS - 1 ? nk - 1 - k : NS - 1;
-    if (after >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PER) : "memory");
-    else if (after == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER) : "memory");
-    else if (after == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (after >= 3) vm_wait<3 * PER>();
+    else if (after == 2) vm_wait<2 * PER>();
+    else if (after == 1) vm_wait<PER>();
+    else vm_wait<0>();
     __builtin_amdgcn_s_barrier();
     const char* TA_ = smem + (k % NS) * STAGE;
     const char* TB_ = TA_ + SA;
@@ -584,9 +547,9 @@ __global__ __launch_bounds__(CNT, 1) void conv_wgrad_taps_kernel(const WgradTaps
   const int split = blockIdx.x % a.splits, grp = blockIdx.x / a.splits;  // tap group: taps NT·grp ..
   const int kq = a.ksteps / a.splits, kr = a.ksteps % a.splits;
   const int k0 = split * kq + min(split, kr), nk = kq + (split < kr ? 1 : 0);
-  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.dy), 0, (int)a.dybytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a.x), 0, (int)a.xbytes, 0x00020000);
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const __amdgpu_buffer_rsrc_t rsY = buf_rsrc(a.dy, (int)a.dybytes);
+  const __amdgpu_buffer_rsrc_t rsX = buf_rsrc(a.x, (int)a.xbytes);
+  const unsigned lds0 = lds_addr(smem);
   // this lane's rows in pieces p = w + 4i: row RPP·p + l / LPR, chunk (l % LPR) ^ swz
   int prow[PW], pch[PW];
 #pragma unroll
@@ -600,7 +563,7 @@ __global__ __launch_bounds__(CNT, 1) void conv_wgrad_taps_kernel(const WgradTaps
     for (int i = 0; i < PW; ++i) {
       const long long t = (long long)kt * 64 + prow[i];
       const unsigned p = (unsigned)((w + 4 * i) * 1024);
-      bufld(t < a.M ? (unsigned)((t * CH + pch[i] * 8) * 2) : OOB, rsY, sb + p);
+      bufld16_lds(t < a.M ? (unsigned)((t * CH + pch[i] * 8) * 2) : OOB, rsY, sb + p);
       int hb = -(1 << 20), wb = 0, base = 0;
       if (t < a.M) {
         int q, wo, n, ho;
@@ -615,7 +578,7 @@ __global__ __launch_bounds__(CNT, 1) void conv_wgrad_taps_kernel(const WgradTaps
       for (int u = 0; u < NT; ++u) {
         const int tap = NT * grp + u, dh = S2D ? u : tap / 3, dw = S2D ? 0 : tap - 3 * dh;
         const bool ok = (unsigned)(hb + dh) < (unsigned)a.IH && (unsigned)(wb + dw) < (unsigned)a.IW;
-        bufld(ok ? (unsigned)((base + (dh * a.IW + dw) * XC) * 2) : OOB, rsX, sb + (unsigned)((1 + u) * TS) + p);
+        bufld16_lds(ok ? (unsigned)((base + (dh * a.IW + dw) * XC) * 2) : OOB, rsX, sb + (unsigned)((1 + u) * TS) + p);
       }
     }
   };
@@ -625,9 +588,7 @@ __global__ __launch_bounds__(CNT, 1) void conv_wgrad_taps_kernel(const WgradTaps
     const int r0 = 32 * kk + 4 * g + q4, r1 = r0 + 16;
     const char* a0 = T + r0 * RB + (((col >> 3) ^ wswz<RB>(r0)) << 4) + (col & 7) * 2;
     const char* a1 = T + r1 * RB + (((col >> 3) ^ wswz<RB>(r1)) << 4) + (col & 7) * 2;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)a0);
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)a1);
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return ld_tr8(a0, a1);
   };
   f32x4 acc[MI][NJ];
 #pragma unroll
@@ -639,9 +600,9 @@ __global__ __launch_bounds__(CNT, 1) void conv_wgrad_taps_kernel(const WgradTaps
   for (int k = 0; k < nk; ++k) {
     if (k + 1 < nk) {
       issue(k0 + k + 1, (k + 1) & 1);
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");  // step k landed (step k + 1 flies)
+      vm_wait<PER>();  // step k landed (step k + 1 flies)
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      vm_wait<0>();
     }
     __builtin_amdgcn_s_barrier();
     const char* S0 = smem + (k & 1) * STAGE;

@@ -29,50 +29,18 @@
 // 165, fc1 546, fc2 523 µs (tools/dw_probe.py).
 #include <stdlib.h>
 
-#include "common.h"
+#include "dw_tile.h"
 #include "kernels.h"
 
 namespace pdo {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int LROW = 256;                 // LDS row (elements) of a [BK][256] tile
 constexpr int TILE = BK * LROW;           // elements per operand tile
 constexpr int NTHR = 512;
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// element offset of (token row r, 16-B chunk ch) in the swizzled LDS tile
-__device__ __forceinline__ int loff(int r, int ch) { return r * LROW + ((ch ^ ((r & 3) << 2)) << 3); }
-
-// per-lane element offset of the transposed fragment for k0 = 0 and columns
-// [cb, cb + 32); tokens k0 + 4·(lane>>5) + q and +8 (q = (lane>>2)&3)
-__device__ __forceinline__ int frag_base(int cb, int lane) {
-  const int g = lane >> 4, t = lane & 15, q = t >> 2, p = t & 3;
-  const int col = cb + 16 * (g & 1) + 4 * p;
-  const int r0 = 4 * (g >> 1) + q;
-  return loff(r0, col >> 3) + (col & 7);
-}
-
-template <int K0>
-__device__ __forceinline__ bf16x8 frag(const bf16* T) {
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(T + K0 * LROW));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(T + (K0 + 8) * LROW));
-  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
+using Tile = DwTile<LROW>;                // swizzle and transposed fragments (dw_tile.h)
 
 __global__ __launch_bounds__(NTHR) void gemm_dw_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                                                        int lda, int ldb, int M, int N, int ksteps_total, int splits,
@@ -83,13 +51,8 @@ __global__ __launch_bounds__(NTHR) void gemm_dw_kernel(const bf16* __restrict__ 
   const int wm = w >> 2, wn = w & 3;
   const int tiles_n = N / BN, tiles_m = M / BM;
   const int nwg = tiles_m * tiles_n * splits;
-  // XCD remap: hardware ids go round-robin over the 8 XCDs; give each XCD a
-  // contiguous range of logical ids (bijective for any nwg)
-  int id = blockIdx.x;
-  {
-    const int xcd = id & 7, slot = id >> 3, q = nwg >> 3, r = nwg & 7;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  // the workgroups sharing an A or B panel run on one XCD (shared L2)
+  const int id = xcd_remap((int)blockIdx.x, nwg);
   const int tn = id % tiles_n;
   const int tm = (id / tiles_n) % tiles_m;
   const int split = id / (tiles_n * tiles_m);
@@ -113,9 +76,9 @@ __global__ __launch_bounds__(NTHR) void gemm_dw_kernel(const bf16* __restrict__ 
     const int r = 2 * (4 * w + i) + (lane >> 5);
     src_off[i] = (((lane & 31) ^ ((r & 3) << 2)) << 3);
   }
-  const int fa[4] = {frag_base(wm * 128 + 0, lane), frag_base(wm * 128 + 32, lane), frag_base(wm * 128 + 64, lane),
-                     frag_base(wm * 128 + 96, lane)};
-  const int fb[2] = {frag_base(wn * 64 + 0, lane), frag_base(wn * 64 + 32, lane)};
+  const int fa[4] = {Tile::frag_base(wm * 128 + 0, lane), Tile::frag_base(wm * 128 + 32, lane),
+                     Tile::frag_base(wm * 128 + 64, lane), Tile::frag_base(wm * 128 + 96, lane)};
+  const int fb[2] = {Tile::frag_base(wn * 64 + 0, lane), Tile::frag_base(wn * 64 + 32, lane)};
 
   f32x16 acc[4][2];
 #pragma unroll
@@ -131,18 +94,12 @@ __global__ __launch_bounds__(NTHR) void gemm_dw_kernel(const bf16* __restrict__ 
   // drained (vmcnt(0)) in step 3's R, one barrier before anyone reads it; its
   // buffer's last reads (previous tile, step 3) retired before the barrier
   // that precedes the DMA issue.
-  // LDS-DMA in inline asm: hipcc does not count these, so it neither drains
-  // them before every ds_read (what it does for the builtin: it cannot prove
-  // the DMA target and the reads apart) nor at the raw barriers — the only
-  // wait is the explicit vmcnt(0) in step 3
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) bf16*)smem;
-  auto glds = [](const bf16* src, unsigned lds_byte) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds_byte)
-                 : "memory");
-  };
+  // LDS-DMA in inline asm (glds16_keep_m0; per-lane pointers, M0 restored):
+  // hipcc does not count these, so it neither drains them before every ds_read
+  // (what it does for the builtin: it cannot prove the DMA target and the reads
+  // apart) nor at the raw barriers — the only wait is the explicit vmcnt(0) in
+  // step 3
+  const unsigned lds0 = lds_addr(smem);
   auto load_half = [&](int kt, int buf, int h) {
     const unsigned abase = lds0 + (unsigned)(buf * 2 * TILE) * 2u, bbase = abase + TILE * 2u;
 #pragma unroll
@@ -150,13 +107,13 @@ __global__ __launch_bounds__(NTHR) void gemm_dw_kernel(const bf16* __restrict__ 
       const int r = 2 * (4 * w + i) + (lane >> 5);
       const size_t row = (size_t)(kt * BK + r);
       const unsigned off = (unsigned)((4 * wu + i) * 512) * 2u;
-      glds(Ab + row * lda + src_off[i], abase + off);
-      glds(Bb + row * ldb + src_off[i], bbase + off);
+      glds16_keep_m0(Ab + row * lda + src_off[i], abase + off);
+      glds16_keep_m0(Bb + row * ldb + src_off[i], bbase + off);
     }
   };
   load_half(0, 0, 0);
   load_half(0, 0, 1);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   __builtin_amdgcn_s_barrier();
   const bool g1 = wu >= 4;
   if (g1) __builtin_amdgcn_s_barrier();
@@ -167,23 +124,26 @@ __global__ __launch_bounds__(NTHR) void gemm_dw_kernel(const bf16* __restrict__ 
     const bf16* Bs = As + TILE;
 #define PDO_DW_PP(KS, PRE)                                                     \
     {                                                                          \
-      bf16x8 a0 = frag<16 * KS>(As + fa[0]), a1 = frag<16 * KS>(As + fa[1]);   \
-      bf16x8 a2 = frag<16 * KS>(As + fa[2]), a3 = frag<16 * KS>(As + fa[3]);   \
-      bf16x8 b0 = frag<16 * KS>(Bs + fb[0]), b1 = frag<16 * KS>(Bs + fb[1]);   \
+      bf16x8 a0 = Tile::frag<16 * KS>(As + fa[0]);                             \
+      bf16x8 a1 = Tile::frag<16 * KS>(As + fa[1]);                             \
+      bf16x8 a2 = Tile::frag<16 * KS>(As + fa[2]);                             \
+      bf16x8 a3 = Tile::frag<16 * KS>(As + fa[3]);                             \
+      bf16x8 b0 = Tile::frag<16 * KS>(Bs + fb[0]);                             \
+      bf16x8 b1 = Tile::frag<16 * KS>(Bs + fb[1]);                             \
       PRE                                                                      \
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                       \
       __builtin_amdgcn_sched_barrier(0);                                       \
       __builtin_amdgcn_s_barrier();                                            \
       __builtin_amdgcn_sched_barrier(0);                                       \
       __builtin_amdgcn_s_setprio(1);                                           \
-      acc[0][0] = mfma(a0, b0, acc[0][0]);                                     \
-      acc[0][1] = mfma(a0, b1, acc[0][1]);                                     \
-      acc[1][0] = mfma(a1, b0, acc[1][0]);                                     \
-      acc[1][1] = mfma(a1, b1, acc[1][1]);                                     \
-      acc[2][0] = mfma(a2, b0, acc[2][0]);                                     \
-      acc[2][1] = mfma(a2, b1, acc[2][1]);                                     \
-      acc[3][0] = mfma(a3, b0, acc[3][0]);                                     \
-      acc[3][1] = mfma(a3, b1, acc[3][1]);                                     \
+      acc[0][0] = mfma32(a0, b0, acc[0][0]);                                     \
+      acc[0][1] = mfma32(a0, b1, acc[0][1]);                                     \
+      acc[1][0] = mfma32(a1, b0, acc[1][0]);                                     \
+      acc[1][1] = mfma32(a1, b1, acc[1][1]);                                     \
+      acc[2][0] = mfma32(a2, b0, acc[2][0]);                                     \
+      acc[2][1] = mfma32(a2, b1, acc[2][1]);                                     \
+      acc[3][0] = mfma32(a3, b0, acc[3][0]);                                     \
+      acc[3][1] = mfma32(a3, b1, acc[3][1]);                                     \
       __builtin_amdgcn_s_setprio(0);                                           \
       __builtin_amdgcn_sched_barrier(0);                                       \
       __builtin_amdgcn_s_barrier();                                            \
@@ -192,7 +152,7 @@ __global__ __launch_bounds__(NTHR) void gemm_dw_kernel(const bf16* __restrict__ 
     PDO_DW_PP(0, if (more) load_half(kt + 1, buf ^ 1, 0);)
     PDO_DW_PP(1, if (more) load_half(kt + 1, buf ^ 1, 1);)
     PDO_DW_PP(2, )
-    PDO_DW_PP(3, asm volatile("s_waitcnt vmcnt(0)" ::: "memory");)
+    PDO_DW_PP(3, vm_wait<0>();)
 #undef PDO_DW_PP
   }
   if (!g1) __builtin_amdgcn_s_barrier();  // balance the stagger

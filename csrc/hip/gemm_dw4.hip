@@ -21,40 +21,19 @@
 // profiles/r2_gemm_nt4.md.)
 #include <type_traits>
 
-#include "common.h"
+#include "dw_tile.h"
 #include "kernels.h"
 
 namespace pdo {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int LROW = 256;             // LDS row (elements) of a [BK][256] tile
 constexpr int TILE = BK * LROW;       // elements per operand tile
 constexpr int OPB = TILE * 2;         // bytes per operand tile (32 KiB)
 constexpr int NTHR = 256;
-
-// element offset of (token row r, 16-B chunk ch) in the swizzled LDS tile
-__device__ __forceinline__ int loff(int r, int ch) { return r * LROW + ((ch ^ ((r & 3) << 2)) << 3); }
-
-// per-lane element offset of the transposed 32x32x16 fragment for columns
-// [cb, cb + 32) at token 0 (gemm_dw.hip frag_base)
-__device__ __forceinline__ int frag_base(int cb, int lane) {
-  const int g = lane >> 4, t = lane & 15, q = t >> 2, p = t & 3;
-  const int col = cb + 16 * (g & 1) + 4 * p;
-  const int r0 = 4 * (g >> 1) + q;
-  return loff(r0, col >> 3) + (col & 7);
-}
-
-template <int K0>
-__device__ __forceinline__ bf16x8 frag(const bf16* T) {
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(T + K0 * LROW));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(T + (K0 + 8) * LROW));
-  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
+using Tile = DwTile<LROW>;            // the 32x32x16 variant's swizzle and fragments (dw_tile.h)
 
 __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                                                            int lda, int ldb, int M, int N, int ksteps_total,
@@ -66,11 +45,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restric
   const int wm = w >> 1, wn = w & 1;
   const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;  // M % 256 == 128: a half-height last row of tiles
   const int nwg = tiles_m * tiles_n * splits;
-  int id = blockIdx.x;
-  {  // bijective XCD remap (gemm_dw.hip)
-    const int xcd = id & 7, slot = id >> 3, q = nwg >> 3, r = nwg & 7;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  const int id = xcd_remap((int)blockIdx.x, nwg);
   const int tn = id % tiles_n;
   const int tm = (id / tiles_n) % tiles_m;
   const int split = id / (tiles_n * tiles_m);
@@ -96,14 +71,8 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restric
   const bf16* baseA = A + ((size_t)k0 * BK + 2 * w) * lda + m0;
   const bf16* baseB = B + ((size_t)k0 * BK + 2 * w) * ldb + n0;
   const unsigned stepAb = (unsigned)(16 * lda), stepBb = (unsigned)(16 * ldb);  // 8 rows, bytes
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) bf16*)smem + (unsigned)(w * 1024);
-  // M0 is not saved around the DMA: nothing else in this kernel uses it
-  auto glds = [](unsigned voff, const bf16* sbase, unsigned lds_byte) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :
-                 : "v"(voff), "s"(sbase), "s"(lds_byte)
-                 : "memory");
-  };
+  const unsigned lds0 = lds_addr(smem) + (unsigned)(w * 1024);
+  // glds16 (M0 not saved around the DMA): nothing else in this kernel uses M0
   struct Src {
     const char* a;
     const char* b;
@@ -118,8 +87,8 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restric
   auto dma = [&](const Src& sr, auto buf_tag, int p) {  // p < 8: A piece p, else B piece p - 8
     constexpr int BUF = decltype(buf_tag)::value;
     const unsigned base = lds0 + (unsigned)(BUF * 2 * OPB);
-    if (p < 8) glds(voffA, reinterpret_cast<const bf16*>(sr.a + p * sr.sa), base + (unsigned)(4096 * p));
-    else glds(voffB, reinterpret_cast<const bf16*>(sr.b + (p - 8) * sr.sb), base + OPB + (unsigned)(4096 * (p - 8)));
+    if (p < 8) glds16(voffA, sr.a + p * sr.sa, base + (unsigned)(4096 * p));
+    else glds16(voffB, sr.b + (p - 8) * sr.sb, base + OPB + (unsigned)(4096 * (p - 8)));
   };
 
   // ---- fragments: block half h (0: tokens 0-31, 1: 32-63) holds k-steps 2h, 2h+1;
@@ -128,20 +97,21 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restric
   int fa[4], fb[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    fa[i] = frag_base(wm * 128 + 32 * i, lane);
-    fb[i] = TILE + frag_base(wn * 128 + 32 * i, lane);
+    fa[i] = Tile::frag_base(wm * 128 + 32 * i, lane);
+    fb[i] = TILE + Tile::frag_base(wn * 128 + 32 * i, lane);
   }
   auto rd = [&](auto buf_tag, int h, int q) -> bf16x8 {
     constexpr int BUF = decltype(buf_tag)::value;
     const bf16* T = smA[BUF] + ((q & 7) < 4 ? fa[q & 3] : fb[q & 3]);
     const int ks = 2 * h + (q >> 3);
     switch (ks) {
-      case 0: return frag<0>(T);
-      case 1: return frag<16>(T);
-      case 2: return frag<32>(T);
-      default: return frag<48>(T);
+      case 0: return Tile::frag<0>(T);
+      case 1: return Tile::frag<16>(T);
+      case 2: return Tile::frag<32>(T);
+      default: return Tile::frag<48>(T);
     }
   };
+  // 32x32x16 forms of cdna4.h's mfma16_acc / mfma16_acc0 (same rules)
   auto mma = [](f32x16& c, const bf16x8& a, const bf16x8& b) {
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
   };
@@ -169,7 +139,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restric
 #pragma unroll
       for (int p = 0; p < 16; ++p) dma(s1, B1{}, p);
     }
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // tile 0 landed (tile 1 may fly)
+    vm_wait<16>();  // tile 0 landed (tile 1 may fly)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -291,9 +261,7 @@ __device__ __forceinline__ int frag_base16(int cb, int lane) {
 }
 template <int K0>
 __device__ __forceinline__ bf16x8 frag16(const bf16* T) {
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(T + K0 * LROW));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(T + (K0 + 16) * LROW));
-  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return ld_tr8(T + K0 * LROW, T + (K0 + 16) * LROW);
 }
 
 // GATHER (the convolution weight gradient, conv.hip's conv_wgrad): B is not a
@@ -311,24 +279,6 @@ struct DwGather {
   float* part;
 };
 
-__device__ __forceinline__ void bufld_lds(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned lds_byte) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs),
-               "s"(lds_byte)
-               : "memory");
-}
-
-__device__ __forceinline__ void divmodf(int x, int d, float inv, int& q, int& r) {
-  q = (int)((float)x * inv);
-  r = x - q * d;
-  if (r < 0) {
-    --q;
-    r += d;
-  } else if (r >= d) {
-    ++q;
-    r -= d;
-  }
-}
-
 template <bool GATHER>
 __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                                                               int lda, int ldb, int M, int N, int ksteps_total,
@@ -341,11 +291,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
   const int wm = w >> 1, wn = w & 1;
   const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;
   const int nwg = tiles_m * tiles_n * splits;
-  int id = blockIdx.x;
-  {  // bijective XCD remap
-    const int xcd = id & 7, slot = id >> 3, q = nwg >> 3, r = nwg & 7;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  const int id = xcd_remap((int)blockIdx.x, nwg);
   const int tn = id % tiles_n;
   const int tm = (id / tiles_n) % tiles_m;
   const int split = id / (tiles_n * tiles_m);
@@ -369,17 +315,10 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
   const bf16* baseA = A + ((size_t)k0 * BK + 2 * w) * lda + m0;
   const bf16* baseB = GATHER ? A : B + ((size_t)k0 * BK + 2 * w) * ldb + n0;
   const unsigned stepAb = (unsigned)(16 * lda), stepBb = (unsigned)(16 * ldb);
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) bf16*)smem + (unsigned)(w * 1024);
-  auto glds = [](unsigned voff, const bf16* sbase, unsigned lds_byte) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :
-                 : "v"(voff), "s"(sbase), "s"(lds_byte)
-                 : "memory");
-  };
+  const unsigned lds0 = lds_addr(smem) + (unsigned)(w * 1024);  // glds16 / bufld16_lds: no other M0 use here either
   // GATHER: per parity, the lane's column chunk → (tap row / column offset, channel)
   int gdh[2] = {0, 0}, gdw[2] = {0, 0}, gci[2] = {0, 0};
-  const __amdgpu_buffer_rsrc_t rsX =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(GATHER ? gx.x : A), 0, GATHER ? (int)gx.xbytes : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsX = buf_rsrc(GATHER ? gx.x : A, GATHER ? (int)gx.xbytes : 0);
   if constexpr (GATHER) {
 #pragma unroll
     for (int par = 0; par < 2; ++par) {
@@ -406,20 +345,20 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
     constexpr int BUF = decltype(buf_tag)::value;
     const unsigned base = lds0 + (unsigned)(BUF * 2 * OPB);
     if (p < 8) {
-      glds(voffA[p & 1], reinterpret_cast<const bf16*>(sr.a + p * sr.sa), base + (unsigned)(4096 * p));
+      glds16(voffA[p & 1], sr.a + p * sr.sa, base + (unsigned)(4096 * p));
     } else if constexpr (GATHER) {
       // B piece p - 8: token rows 8(p - 8) + 2w + rl of k-tile k0 + kt
       const int t = (k0 + sr.kt) * BK + 8 * (p - 8) + rw;
       int q, wo, n, ho;
-      divmodf(t, gx.TB, gx.inv_TB, q, wo);
-      divmodf(q, gx.TA, gx.inv_TA, n, ho);
+      divmod(t, gx.TB, gx.inv_TB, q, wo);
+      divmod(q, gx.TA, gx.inv_TA, n, ho);
       const int hi = ho * gx.st + gdh[p & 1], wi = wo * gx.st + gdw[p & 1];
       const unsigned off = ((unsigned)hi < (unsigned)gx.IH && (unsigned)wi < (unsigned)gx.IW)
                                ? (unsigned)((((n * gx.IH + hi) * gx.IW + wi) * gx.C + gci[p & 1]) * 2)
                                : 0x80000000u;
-      bufld_lds(off, rsX, base + OPB + (unsigned)(4096 * (p - 8)));
+      bufld16_lds(off, rsX, base + OPB + (unsigned)(4096 * (p - 8)));
     } else {
-      glds(voffB[p & 1], reinterpret_cast<const bf16*>(sr.b + (p - 8) * sr.sb), base + OPB + (unsigned)(4096 * (p - 8)));
+      glds16(voffB[p & 1], sr.b + (p - 8) * sr.sb, base + OPB + (unsigned)(4096 * (p - 8)));
     }
   };
 
@@ -437,12 +376,6 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
     const bf16* T = smA[BUF] + fo[q];
     return h ? frag16<32>(T) : frag16<0>(T);
   };
-  auto mma = [](f32x4& c, const bf16x8& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-  };
-  auto mma0 = [](f32x4& c, const bf16x8& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
-  };
   using B0 = std::integral_constant<int, 0>;
   using B1 = std::integral_constant<int, 1>;
 
@@ -456,7 +389,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
 #pragma unroll
     for (int p = 0; p < 16; ++p) dma(s1, B1{}, p);
   }
-  asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // tile 0 landed (tile 1 may fly)
+  vm_wait<16>();  // tile 0 landed (tile 1 may fly)
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
@@ -482,8 +415,8 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
       const int mb = g >> 1, nb0 = 4 * (g & 1);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        if (FIRST) mma0(acc[mb][nb0 + u], f0[mb], f0[8 + nb0 + u]);
-        else mma(acc[mb][nb0 + u], f0[mb], f0[8 + nb0 + u]);
+        if (FIRST) mfma16_acc0(acc[mb][nb0 + u], f0[mb], f0[8 + nb0 + u]);
+        else mfma16_acc(acc[mb][nb0 + u], f0[mb], f0[8 + nb0 + u]);
       }
       f1[g] = rd(buf_tag, 1, g);
       if constexpr (EOUT) {
@@ -505,7 +438,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
     for (int g = 0; g < 16; ++g) {
       const int mb = g >> 1, nb0 = 4 * (g & 1);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) mma(acc[mb][nb0 + u], f1[mb], f1[8 + nb0 + u]);
+      for (int u = 0; u < 4; ++u) mfma16_acc(acc[mb][nb0 + u], f1[mb], f1[8 + nb0 + u]);
       if constexpr (MORE) f0[g] = rd(NB{}, 0, g);
       if constexpr (EOUT) {
         if (g & 1) dma(sn2, SB{}, (g >> 1) < 4 ? (g >> 1) + 4 : (g >> 1) + 8);  // second-half pieces

@@ -46,7 +46,7 @@
 // contracts are pinned bit for bit by tests/test_gemm_nt_exact_gpu.py.
 #include <stdlib.h>
 
-#include "common.h"
+#include "cdna4.h"
 #include "kernels.h"
 
 namespace pdo {
@@ -74,13 +74,9 @@ __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(const bf16* __restrict__ 
   const int li = lane & 31, hh = lane >> 5;
   const int tiles_n = N / BN;
   const int nwg = (M / BM) * tiles_n;
-  // XCD remap (gemm_dw.hip): each XCD gets a contiguous range of logical ids,
-  // i.e. the N-tiles of a few A row panels, which then share its L2
-  int id = blockIdx.x;
-  {
-    const int xcd = id & 7, slot = id >> 3, q = nwg >> 3, r = nwg & 7;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  // each XCD gets a contiguous range of logical ids, i.e. the N-tiles of a few
+  // A row panels, which then share its L2
+  const int id = xcd_remap((int)blockIdx.x, nwg);
   const int tn = id % tiles_n, tm = id / tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
 
@@ -107,31 +103,25 @@ __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(const bf16* __restrict__ 
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) bf16*)smem;
-  auto glds = [](const bf16* src, unsigned lds_byte) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds_byte)
-                 : "memory");
-  };
-  // one 32-k stage = 4 DMA wave-instructions per wave (2 A + 2 B)
+  const unsigned lds0 = lds_addr(smem);
+  // one 32-k stage = 4 DMA wave-instructions per wave (2 A + 2 B), per-lane
+  // pointers with M0 restored (glds16_keep_m0)
   auto load_stage = [&](int s) {
     const unsigned abase = lds0 + (unsigned)((s % STAGES) * 2 * TILE) * 2u, bbase = abase + TILE * 2u;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const unsigned off = (unsigned)((2 * wu + i) * 1024);
-      glds(srcA[i] + (size_t)s * BK, abase + off);
-      glds(srcB[i] + (size_t)s * BK, bbase + off);
+      glds16_keep_m0(srcA[i] + (size_t)s * BK, abase + off);
+      glds16_keep_m0(srcB[i] + (size_t)s * BK, bbase + off);
     }
   };
   // wait until this wave's DMA for stage `s` landed, given stages ≤ last issued
   auto wait_stage = [](int after) {  // after = stages issued after it (0..STAGES-2)
     static_assert(STAGES == 5, "wait_stage covers 0..3 stages in flight after the awaited one");
-    if (after >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (after == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (after == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (after >= 3) vm_wait<12>();
+    else if (after == 2) vm_wait<8>();
+    else if (after == 1) vm_wait<4>();
+    else vm_wait<0>();
   };
   // Ping-pong over a STAGES-deep ring of 32-k stages: waves 4-7 run one barrier
   // interval behind waves 0-3, so on every SIMD one wave issues its 32 MFMAs

@@ -50,7 +50,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "cdna4.h"
 #include "kernels.h"
 
 namespace pdo {
@@ -58,20 +58,7 @@ namespace pdo {
 namespace {
 
 constexpr int BM = 256, BN = 256, BK = 64, NTHR = 256;
-
-// f(integral_constant<int, I>) for I = 0 .. N-1, expanded at compile time: a
-// 128-slot MFMA schedule is too large for `#pragma unroll` (hipcc gives up and
-// indexes the accumulators at run time); here every slot's index is a constant
-template <typename Fn, int... I>
-__device__ __forceinline__ void static_for_impl(Fn&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename Fn>
-__device__ __forceinline__ void static_for(Fn&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 constexpr int OPB = 256 * BK * 2;  // bytes of one operand tile [256][64] bf16 = 32 KiB
-
 
 // MIR: runs of 8 MFMAs share the SrcA operand (A fragment i, as hipBLASLt's
 //      loop does) and the operands trade places in the read / release / refill
@@ -91,11 +78,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
   const int tiles_n = (N + BN - 1) / BN;  // N % 256 = 128 allowed (half-width last tile column)
   const int nwg = (M / BM) * tiles_n;
   auto coords = [&](int v, int& tm_, int& tn_) {
-    int id = v;
-    {  // bijective XCD remap: each XCD walks a contiguous range of tiles (shared A panels in its L2)
-      const int xcd = id & 7, slot = id >> 3, q = nwg >> 3, r = nwg & 7;
-      id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
+    const int id = xcd_remap(v, nwg);  // each XCD walks a contiguous range of tiles (shared A panels in its L2)
     // grouped tile order: consecutive ids walk group_m tile rows, then the next
     // tile column, so the 32 tiles an XCD runs at once form a group_m × (32 /
     // group_m) block and share fewer A/B panels in that XCD's 4 MiB L2
@@ -144,16 +127,9 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
   const bf16* baseB = B + ((size_t)n0 + 64 * (w & 1) + (w >> 1)) * ldb;
   const unsigned stepAb = (unsigned)(64 * lda);  // 32 rows, bytes
   const unsigned stepBb = (unsigned)(4 * ldb);   // 2 rows, bytes
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) bf16*)smem + (unsigned)(w * 1024);
-  // M0 is not saved around the DMA: nothing else in this kernel uses it (check
-  // the .s for other M0 readers after editing); s_nop 0 = the SALU M0 write →
-  // LDS-DMA wait state
-  auto glds = [](unsigned voff, const bf16* sbase, unsigned lds_byte) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :
-                 : "v"(voff), "s"(sbase), "s"(lds_byte)
-                 : "memory");
-  };
+  const unsigned lds0 = lds_addr(smem) + (unsigned)(w * 1024);
+  // glds16 (M0 not saved around the DMA): nothing else in this kernel uses M0
+  auto glds = [](unsigned voff, const void* sbase, unsigned lds_byte) { glds16(voff, sbase, lds_byte); };
   // pieces of tile kt into buffer BUF: p < 8 → A block w + 4p, else B block w + 4(p - 8).
   // The per-tile bases and strides pass through an empty asm so hipcc forms each
   // piece's 64-bit base with two scalar adds next to its DMA instead of keeping
@@ -174,11 +150,11 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
     constexpr int BUF = decltype(buf_tag)::value;
     const unsigned base = lds0 + (unsigned)(BUF * 2 * OPB);
     if (p < 8) {
-      glds(voffA, reinterpret_cast<const bf16*>(sr.a + p * sr.sa), base + (unsigned)(4096 * p));
+      glds(voffA, sr.a + p * sr.sa, base + (unsigned)(4096 * p));
     } else {
       const int pp = p - 8;
       const unsigned mul = (unsigned)((pp & 3) + (dhalfn ? 0 : 64) * (pp >> 2));
-      glds(voffB, reinterpret_cast<const bf16*>(sr.b + mul * sr.sb), base + OPB + (unsigned)(4096 * pp));
+      glds(voffB, sr.b + mul * sr.sb, base + OPB + (unsigned)(4096 * pp));
     }
   };
 
@@ -188,20 +164,17 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
   const int ra = (wm * 128 + (lane & 15)) * 128, rbb = (wn * 128 + (lane & 15)) * 128;
   const int oA0 = ra + ((((lane >> 4)) ^ sw) << 4), oA1 = ra + (((4 + (lane >> 4)) ^ sw) << 4);
   const int oB0 = OPB + rbb + ((((lane >> 4)) ^ sw) << 4), oB1 = OPB + rbb + (((4 + (lane >> 4)) ^ sw) << 4);
-  // MFMA with the accumulator pinned to the accumulator file ("+a"): with the
-  // builtin, hipcc kept part of the 256 accumulators in arch VGPRs and shuttled
-  // them through v_accvgpr_read/write around every MFMA (≈3 VALU per MFMA).
-  // hipcc does not see inside the asm, so the asm must not depend on its hazard
-  // padding: the operands come from ds_read (hipcc's lgkmcnt waits cover asm
-  // inputs), an accumulator is rewritten 64 MFMAs after its previous write, the
-  // first write of each one takes C = 0 (mma0: no v_accvgpr_write init that a
-  // following MFMA would read too early), and the epilogue pads before reading.
-  auto mma = [](f32x4& c, const bf16x8& b, const bf16x8& a) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(b), "v"(a));
-  };
-  auto mma0 = [](f32x4& c, const bf16x8& b, const bf16x8& a) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(b), "v"(a));
-  };
+  // MFMA with the accumulator pinned to the accumulator file (mfma16_acc /
+  // mfma16_acc0): with the builtin, hipcc kept part of the 256 accumulators in
+  // arch VGPRs and shuttled them through v_accvgpr_read/write around every MFMA
+  // (≈3 VALU per MFMA).  Their rules hold here: the operands come from ds_read
+  // (hipcc's lgkmcnt waits cover asm inputs), an accumulator is rewritten 64
+  // MFMAs after its previous write, the first write of each one takes C = 0,
+  // and the epilogue pads before reading.
+  // (lambdas, here and for glds: hipcc inlines a lambda later than a forced-inline
+  // function, and this kernel's register allocation depends on it)
+  auto mma = [](f32x4& c, const bf16x8& b, const bf16x8& a) { mfma16_acc(c, b, a); };
+  auto mma0 = [](f32x4& c, const bf16x8& b, const bf16x8& a) { mfma16_acc0(c, b, a); };
   using B0 = std::integral_constant<int, 0>;
   using B1 = std::integral_constant<int, 1>;
 
@@ -486,11 +459,11 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
         // flight; wave 0 of a ticket tile: those and the ticket's atomic)
         if constexpr (LOAD) {
           if (dyn && tk && w == 0)
-            asm volatile("s_waitcnt vmcnt(17)" ::: "memory");
+            vm_wait<17>();
           else
-            asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+            vm_wait<16>();
         } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          vm_wait<0>();
         }
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -545,7 +518,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
   issue01();
   for (;;) {
     // tile 0 landed (tile 1 may fly)
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    vm_wait<16>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);

@@ -10,7 +10,7 @@
 #include "philox.h"
 
 namespace pdo {
-typedef __bf16 bf16;
+typedef __bf16 bf16;  // also in common.h: bind.cpp includes this header alone, without the device helpers
 
 // Destination of a column sum: columns [k·seg, (k+1)·seg) go to p[k] (≤ 3
 // segments, seg % 4 == 0); acc = add into the existing bf16 values.

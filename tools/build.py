@@ -63,12 +63,9 @@ def torch_flags():
     return cflags, ldflags
 
 
-def build_hip(jobs=8, verbose=False):
-    src_dir = os.path.join(ROOT, "csrc", "hip")
-    obj_dir = os.path.join(BUILD, "hip")
-    os.makedirs(obj_dir, exist_ok=True)
-    headers = glob.glob(os.path.join(src_dir, "*.h"))
-    kernels = sorted(glob.glob(os.path.join(src_dir, "*.hip")))
+def hip_flags(name):
+    """hipcc flags for the csrc/hip file with base name `name` (tools/isa_stats.py
+    and tools/isa_diff.py compile with the same list)."""
     common = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-gpu-rdc",
               "-Wno-unused-result", "-munsafe-fp-atomics"]
     # MFMA accumulators in arch VGPRs: no v_accvgpr copies around the VALU work
@@ -81,17 +78,26 @@ def build_hip(jobs=8, verbose=False):
     # per-file extras: attention's softmax max-reductions become v_max3 only
     # without NaN canonicalisation (scores are never NaN; ±inf masks keep working)
     extra = {"attention.hip": ["-fno-honor-nans"]}
+    form = [] if name in agpr_files else vgpr_form
+    return common + form + extra.get(name, [])
+
+
+def build_hip(jobs=8, verbose=False):
+    src_dir = os.path.join(ROOT, "csrc", "hip")
+    obj_dir = os.path.join(BUILD, "hip")
+    os.makedirs(obj_dir, exist_ok=True)
+    headers = glob.glob(os.path.join(src_dir, "*.h"))
+    kernels = sorted(glob.glob(os.path.join(src_dir, "*.hip")))
     jobs_list = []
     for s in kernels:
         o = os.path.join(obj_dir, os.path.basename(s) + ".o")
         if _newer(o, [s] + headers + [os.path.abspath(__file__)]):
-            form = [] if os.path.basename(s) in agpr_files else vgpr_form
-            jobs_list.append([HIPCC] + common + form + extra.get(os.path.basename(s), []) + ["-c", s, "-o", o])
+            jobs_list.append([HIPCC] + hip_flags(os.path.basename(s)) + ["-c", s, "-o", o])
     tcf, tld = torch_flags()
     bind = os.path.join(src_dir, "bind.cpp")
     bind_o = os.path.join(obj_dir, "bind.o")
     if _newer(bind_o, [bind] + headers):
-        jobs_list.append([HIPCC] + common + vgpr_form + tcf + ["-x", "hip", "-c", bind, "-o", bind_o])
+        jobs_list.append([HIPCC] + hip_flags("bind.cpp") + tcf + ["-x", "hip", "-c", bind, "-o", bind_o])
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         for out in ex.map(_run, jobs_list):
             if verbose and out.strip():

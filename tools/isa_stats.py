@@ -46,15 +46,11 @@ def main():
     ap.add_argument("--blocks", action="store_true")
     ap.add_argument("--flags", default="")
     a = ap.parse_args()
-    from tools.build import ARCH
-    flags = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-munsafe-fp-atomics",
-             "-mllvm", "-amdgpu-mfma-vgpr-form", "-I", os.path.join(ROOT, "csrc", "hip")]
-    if os.path.basename(a.src) == "attention.hip":
-        flags.append("-fno-honor-nans")
-    flags += a.flags.split()
+    from tools.build import HIPCC, hip_flags
+    flags = hip_flags(os.path.basename(a.src)) + ["-I", os.path.join(ROOT, "csrc", "hip")] + a.flags.split()
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
-        subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["--cuda-device-only", "-S", "-o", out, a.src], check=True,
+        subprocess.run([HIPCC] + flags + ["--cuda-device-only", "-S", "-o", out, a.src], check=True,
                        stderr=subprocess.DEVNULL)
         s = open(out).read()
     for m in re.finditer(r"^(_Z\w+):", s, re.M):
