@@ -428,6 +428,55 @@ bool gemm_dw(at::Tensor dy, at::Tensor x, at::Tensor out, bool accumulate, int64
   return true;
 }
 
+// outs[i][M_i][N_i] (+)= dys[i]ᵀ·xs[i] for every i in one launch per DW_GROUP_MAX
+// problems, each output tile over its whole token axis (gemm_dw4_grouped: no
+// split-K, one rounding).  Operands are 2-D bf16 with unit column stride (row
+// strides may exceed the row: arena-slice views).  false = some problem is outside
+// the contract, and then nothing is launched.  Problems whose destinations overlap
+// go to different launches, in list order.
+bool gemm_dw_grouped(std::vector<at::Tensor> dys, std::vector<at::Tensor> xs, std::vector<at::Tensor> outs,
+                     std::vector<bool> accumulates) {
+  const size_t n = dys.size();
+  TORCH_CHECK(xs.size() == n && outs.size() == n && accumulates.size() == n, "gemm_dw_grouped: list lengths differ");
+  auto rows2d = [](const at::Tensor& t) {
+    return t.dim() == 2 && t.size(0) > 0 && t.size(1) > 0 && t.stride(1) == 1 && t.stride(0) >= t.size(1) &&
+           t.stride(0) < (1LL << 24);  // the kernel's 32-bit byte offsets span 8 rows × 16 pieces
+  };
+  std::vector<pdo::DwProblem> ps(n);
+  for (size_t i = 0; i < n; ++i) {
+    const at::Tensor &dy = dys[i], &x = xs[i], &out = outs[i];
+    CHECK_DEV(dy); CHECK_DEV(x); CHECK_DEV(out); CHECK_BF16(dy); CHECK_BF16(x); CHECK_BF16(out);
+    TORCH_CHECK(dy.device() == out.device() && x.device() == out.device(), "gemm_dw_grouped: operands on different devices");
+    TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && out.dim() == 2 && dy.size(0) == x.size(0) &&
+                out.size(0) == dy.size(1) && out.size(1) == x.size(1), "gemm_dw_grouped: out must be [M, N] of dy [T, M], x [T, N]");
+    if (!rows2d(dy) || !rows2d(x) || !rows2d(out)) return false;
+    // the LDS-DMA fetches 16-B chunks: operand rows start on 16-B boundaries
+    auto al16 = [](const at::Tensor& t) { return (uintptr_t)t.data_ptr() % 16 == 0 && t.stride(0) % 8 == 0; };
+    if (!al16(dy) || !al16(x)) return false;
+    const long long T = dy.size(0);
+    if (dy.size(1) >= (1LL << 31) || x.size(1) >= (1LL << 31)) return false;
+    const int M = (int)dy.size(1), N = (int)x.size(1);
+    if (!pdo::gemm_dw4_grouped_ok(T, M, N)) return false;
+    ps[i] = pdo::DwProblem{bp(dy), bp(x), bp(out), T, M, N, (int)dy.stride(0), (int)x.stride(0), (int)out.stride(0),
+                           accumulates[i] ? 1 : 0};
+  }
+  auto overlap = [](const pdo::DwProblem& a, const pdo::DwProblem& b) {
+    const bf16* ae = a.C + (size_t)(a.M - 1) * a.ldc + a.N;
+    const bf16* be = b.C + (size_t)(b.M - 1) * b.ldc + b.N;
+    return a.C < be && b.C < ae;
+  };
+  size_t i0 = 0;
+  for (size_t i = 0; i <= n; ++i) {
+    bool cut = i == n;
+    for (size_t k = i0; k < i && !cut; ++k) cut = overlap(ps[k], ps[i]);
+    if (cut && i > i0) {
+      CHECK_RC(pdo::gemm_dw4_grouped(ps.data() + i0, (int)(i - i0), cur_stream()), "gemm_dw_grouped");
+      i0 = i;
+    }
+  }
+  return true;
+}
+
 // every matrix of `table` (int64 [n, 5]: first tile, src offset, dst offset, R, C)
 // transposed from src into dst in one launch (ops: the step's Wᵀ operands).
 // `host` is the CPU tensor the device `table` was copied from: the entries are
@@ -1431,6 +1480,8 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.def("axpy_dev_", &axpy_dev_);
   m.def("gemm_dw", &gemm_dw, py::arg("dy"), py::arg("x"), py::arg("out"), py::arg("accumulate") = true,
         py::arg("splits") = 0);
+  m.def("gemm_dw_grouped", &gemm_dw_grouped, py::arg("dys"), py::arg("xs"), py::arg("outs"), py::arg("accumulates"));
+  m.def("gemm_dw_grouped_ok", &pdo::gemm_dw4_grouped_ok);
   m.def("gemm_dw_splits", &pdo::gemm_dw_splits);
   m.def("gemm_nt_supported", &gemm_nt_supported);
   m.def("gemm_nt_stats", &gemm_nt_stats);

@@ -279,25 +279,87 @@ struct DwGather {
   float* part;
 };
 
-template <bool GATHER>
-__global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
-                                                              int lda, int ldb, int M, int N, int ksteps_total,
-                                                              int splits, bf16* __restrict__ C, int ldc,
-                                                              long long split_stride, int accumulate,
-                                                              const DwGather gx) {
+// GROUPED: several independent problems in one launch (gemm_dw4_grouped), each
+// workgroup one output tile over its problem's whole token axis.  The table is a
+// kernel argument; first[i] = tiles of problems 0 .. i-1.
+struct DwGroupEntry {
+  const bf16* A;
+  const bf16* B;
+  bf16* C;
+  int lda, ldb, ldc, M, N, ksteps, accumulate;
+};
+struct DwGroupTable {
+  int n;
+  int first[DW_GROUP_MAX + 1];
+  DwGroupEntry p[DW_GROUP_MAX];
+};
+struct DwNoGroup {};
+
+// Grouped workgroup id → tile of the concatenated problems.  The hardware deals
+// workgroup b to XCD b & 7, and an XCD's 32 CUs hold its slots 32r .. 32r + 31
+// together: those 32 get consecutive tiles (the last, partial round of 256 is dealt
+// as xcd_remap deals a whole grid).
+__device__ __forceinline__ int dw_group_tile(int b, int total) {
+  const int full = total & ~255;
+  if (b < full) return (b & ~255) + ((b & 7) << 5) + ((b >> 3) & 31);
+  return full + xcd_remap(b - full, total - full);
+}
+// Tile t of a problem → (tm, tn): strips of 4 tile columns, row-major inside a
+// strip, so 32 consecutive tiles are an 8 × 4 block where the shape has one (two
+// 4 × 4 blocks side by side for a 4-row problem); the last strip may be narrower.
+__device__ __forceinline__ void dw_group_mn(int t, int tiles_m, int tiles_n, int& tm, int& tn) {
+  const int fulls = tiles_n >> 2, per = 4 * tiles_m;
+  if (t < fulls * per) {
+    const int s = t / per, r = t - s * per;
+    tm = r >> 2;
+    tn = 4 * s + (r & 3);
+  } else {
+    const int r = t - fulls * per, wd = tiles_n & 3;
+    tm = r / wd;
+    tn = 4 * fulls + r - tm * wd;
+  }
+}
+
+// SWAP (the grouped launch): the MFMA takes the x fragment as its row operand, so a
+// lane's 4 accumulator registers are 4 adjacent columns of one output row (one 8-B
+// store) instead of 4 rows of one column; the products and their order are the same.
+// The split-K instantiation keeps its layout: with short slices the wide stores
+// measured no faster there (16 single GEMMs: 5105 vs 5064 us, profiles/r13_grouped_dw.md).
+template <bool GATHER, bool GROUPED>
+__global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(
+    const bf16* __restrict__ A_, const bf16* __restrict__ B_, int lda_, int ldb_, int M_, int N_, int ksteps_total,
+    int splits, bf16* __restrict__ C_, int ldc_, long long split_stride, int accumulate_, const DwGather gx,
+    const std::conditional_t<GROUPED, DwGroupTable, DwNoGroup> tb) {
   __shared__ __attribute__((aligned(16))) bf16 smem[2 * 2 * TILE];  // [buf][A|B][BK][256]
+  constexpr bool SWAP = GROUPED;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w >> 1, wn = w & 1;
-  const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;
-  const int nwg = tiles_m * tiles_n * splits;
-  const int id = xcd_remap((int)blockIdx.x, nwg);
-  const int tn = id % tiles_n;
-  const int tm = (id / tiles_n) % tiles_m;
-  const int split = id / (tiles_n * tiles_m);
-  const int pq = (ksteps_total >> 1) / splits, pr = (ksteps_total >> 1) % splits;
-  const int k0 = 2 * (split * pq + min(split, pr));
-  const int nk = 2 * (pq + (split < pr ? 1 : 0));
+  const bf16* A = A_;
+  const bf16* B = B_;
+  bf16* C = C_;
+  int lda = lda_, ldb = ldb_, ldc = ldc_, M = M_, N = N_, accumulate = accumulate_;
+  int tm, tn, split, k0, nk;
+  if constexpr (GROUPED) {
+    const int g = dw_group_tile((int)blockIdx.x, tb.first[tb.n]);
+    int pi = 0;
+    while (g >= tb.first[pi + 1]) ++pi;  // ≤ DW_GROUP_MAX scalar steps
+    const DwGroupEntry& e = tb.p[pi];
+    A = e.A, B = e.B, C = e.C;
+    lda = e.lda, ldb = e.ldb, ldc = e.ldc, M = e.M, N = e.N, accumulate = e.accumulate;
+    dw_group_mn(g - tb.first[pi], (M + BM - 1) / BM, N / BN, tm, tn);
+    split = 0, k0 = 0, nk = e.ksteps;
+  } else {
+    const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;
+    const int nwg = tiles_m * tiles_n * splits;
+    const int id = xcd_remap((int)blockIdx.x, nwg);
+    tn = id % tiles_n;
+    tm = (id / tiles_n) % tiles_m;
+    split = id / (tiles_n * tiles_m);
+    const int pq = (ksteps_total >> 1) / splits, pr = (ksteps_total >> 1) % splits;
+    k0 = 2 * (split * pq + min(split, pr));
+    nk = 2 * (pq + (split < pr ? 1 : 0));
+  }
   const int m0 = tm * BM, n0 = tn * BN;
 
   // LDS-DMA: piece i of an operand = rows 8i + 2w + rl (rl = l >> 5), LDS chunk
@@ -415,8 +477,10 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
       const int mb = g >> 1, nb0 = 4 * (g & 1);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        if (FIRST) mfma16_acc0(acc[mb][nb0 + u], f0[mb], f0[8 + nb0 + u]);
-        else mfma16_acc(acc[mb][nb0 + u], f0[mb], f0[8 + nb0 + u]);
+        const bf16x8& fr = f0[SWAP ? 8 + nb0 + u : mb];
+        const bf16x8& fc = f0[SWAP ? mb : 8 + nb0 + u];
+        if (FIRST) mfma16_acc0(acc[mb][nb0 + u], fr, fc);
+        else mfma16_acc(acc[mb][nb0 + u], fr, fc);
       }
       f1[g] = rd(buf_tag, 1, g);
       if constexpr (EOUT) {
@@ -438,7 +502,8 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
     for (int g = 0; g < 16; ++g) {
       const int mb = g >> 1, nb0 = 4 * (g & 1);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) mfma16_acc(acc[mb][nb0 + u], f1[mb], f1[8 + nb0 + u]);
+      for (int u = 0; u < 4; ++u)
+        mfma16_acc(acc[mb][nb0 + u], f1[SWAP ? 8 + nb0 + u : mb], f1[SWAP ? mb : 8 + nb0 + u]);
       if constexpr (MORE) f0[g] = rd(NB{}, 0, g);
       if constexpr (EOUT) {
         if (g & 1) dma(sn2, SB{}, (g >> 1) < 4 ? (g >> 1) + 4 : (g >> 1) + 8);  // second-half pieces
@@ -458,6 +523,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
   tileH(nk - 1, B1{}, F_{}, F_{}, F_{});
 
   // ---- epilogue: acc[mb][nb][r] = C[m0 + wm·128 + 16mb + 4(l >> 4) + r][n0 + wn·128 + 16nb + (l & 15)]
+  // (with SWAP the lane's row and column roles are exchanged, see the last block)
   asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
   bf16* Cb = C + (size_t)split * split_stride;
   const int g4 = lane >> 4, li = lane & 15;
@@ -480,6 +546,30 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
       }
     return;
   }
+  if constexpr (!SWAP) {
+#pragma unroll
+    for (int mb = 0; mb < 8; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < 8; ++nb) {
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v[r]) : "a"(acc[mb][nb][r]));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = m0 + wm * 128 + 16 * mb + 4 * g4 + r;
+          bf16* p = Cb + (size_t)m * ldc + n0 + wn * 128 + 16 * nb + li;
+          float x = v[r];
+          if (accumulate) x += (float)*p;
+          *p = (bf16)x;
+        }
+      }
+    return;
+  }
+  // SWAP: acc[mb][nb][r] = C[m0 + wm·128 + 16mb + (l & 15)][n0 + wn·128 + 16nb + 4(l >> 4) + r] —
+  // 4 adjacent columns: one 8-B load (accumulate) and one 8-B store per lane, 64 of
+  // them where the layout above takes 256 2-B stores (four layers grouped, isolated:
+  // 4834 vs 4947 us, profiles/r13_grouped_dw.md)
+  const bool al8 = ((reinterpret_cast<size_t>(Cb) | ((size_t)ldc * 2)) & 7) == 0;  // workgroup-uniform
 #pragma unroll
   for (int mb = 0; mb < 8; ++mb)
 #pragma unroll
@@ -487,13 +577,26 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(const bf16* __rest
       float v[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v[r]) : "a"(acc[mb][nb][r]));
+      const int m = m0 + wm * 128 + 16 * mb + li;
+      bf16* q = Cb + (size_t)m * ldc + n0 + wn * 128 + 16 * nb + 4 * g4;
+      if (al8) {
+        bf16x4* p = reinterpret_cast<bf16x4*>(q);
+        if (accumulate) {
+          const bf16x4 o = *p;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * 128 + 16 * mb + 4 * g4 + r;
-        bf16* p = Cb + (size_t)m * ldc + n0 + wn * 128 + 16 * nb + li;
-        float x = v[r];
-        if (accumulate) x += (float)*p;
-        *p = (bf16)x;
+          for (int r = 0; r < 4; ++r) v[r] += (float)o[r];
+        }
+        bf16x4 y;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) y[r] = (bf16)v[r];
+        *p = y;
+      } else {  // a destination or row stride that is not 8-B aligned: element stores
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float x = v[r];
+          if (accumulate) x += (float)q[r];
+          q[r] = (bf16)x;
+        }
       }
     }
 }
@@ -525,9 +628,45 @@ int gemm_dw4(const bf16* A, const bf16* B, long long T, int M, int N, int lda, i
   if (variant == 1)  // the same schedule on 32x32x16 MFMAs (A/B alternative)
     gemm_dw4_kernel<<<grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, (int)ks, splits, out, ldo, stride, acc);
   else
-    gemm_dw4m16_kernel<false><<<grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, (int)ks, splits, out, ldo, stride, acc,
-                                                     DwGather{});
+    gemm_dw4m16_kernel<false, false><<<grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, (int)ks, splits, out, ldo, stride,
+                                                            acc, DwGather{}, DwNoGroup{});
   if (splits > 1) return splitk_add(ws, splits, (long long)M * N, C, accumulate, st);
+  return 0;
+}
+
+bool gemm_dw4_grouped_ok(long long T, int M, int N) {
+  return M > 0 && N > 0 && M % (BM / 2) == 0 && N % BN == 0 && T % (2 * BK) == 0 && T >= 4 * BK &&
+         T / BK <= 0x7fffffffLL;
+}
+
+int gemm_dw4_grouped(const DwProblem* probs, int n, hipStream_t st) {
+  if (n < 0) return -2;
+  for (int i = 0; i < n; ++i) {
+    const DwProblem& q = probs[i];
+    if (!gemm_dw4_grouped_ok(q.T, q.M, q.N) || q.lda < q.M || q.ldb < q.N || q.ldc < q.N || !q.A || !q.B || !q.C)
+      return -2;
+    // per-lane DMA offsets and piece steps are 32-bit byte counts
+    if ((long long)q.lda * 16 * 8 >= (1LL << 31) || (long long)q.ldb * 16 * 8 >= (1LL << 31)) return -2;
+  }
+  for (int i0 = 0; i0 < n;) {
+    DwGroupTable tb;
+    tb.n = 0;
+    tb.first[0] = 0;
+    while (i0 < n && tb.n < DW_GROUP_MAX) {
+      const DwProblem& q = probs[i0];
+      const long long tiles = (long long)((q.M + BM - 1) / BM) * (q.N / BN);
+      if (tb.first[tb.n] + tiles > (1 << 24)) {
+        if (tb.n == 0) return -2;  // one problem of more than 2^24 tiles
+        break;
+      }
+      tb.p[tb.n] = DwGroupEntry{q.A, q.B, q.C, q.lda, q.ldb, q.ldc, q.M, q.N, (int)(q.T / BK), q.accumulate};
+      tb.first[tb.n + 1] = tb.first[tb.n] + (int)tiles;
+      ++tb.n;
+      ++i0;
+    }
+    gemm_dw4m16_kernel<false, true><<<tb.first[tb.n], NTHR, 0, st>>>(nullptr, nullptr, 0, 0, 0, 0, 0, 1, nullptr, 0, 0,
+                                                                    0, DwGather{}, tb);
+  }
   return 0;
 }
 
@@ -563,8 +702,8 @@ int conv_wgrad_dw4(const bf16* dy, const bf16* x, int N, int H, int W, int C, in
   DwGather g{x, (unsigned)((long long)N * H * W * C * 2), C, S, H, W, Ho, Wo, TC, 1.f / (float)Ho, 1.f / (float)Wo,
              stride, pad, part};
   const int grid = ((Kout + BM - 1) / BM) * (TCp / BN) * splits;
-  gemm_dw4m16_kernel<true><<<grid, NTHR, 0, st>>>(dy, nullptr, Kout, 0, Kout, TCp, (int)ks, splits, nullptr, TCp,
-                                                  (long long)Kout * TCp, 0, g);
+  gemm_dw4m16_kernel<true, false><<<grid, NTHR, 0, st>>>(dy, nullptr, Kout, 0, Kout, TCp, (int)ks, splits, nullptr,
+                                                         TCp, (long long)Kout * TCp, 0, g, DwNoGroup{});
   return 0;
 }
 

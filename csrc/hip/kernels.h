@@ -168,6 +168,23 @@ int gemm_dw(const bf16* A, const bf16* B, long long T, int M, int N, int lda, in
 // gemm_dw4.hip: the same contract on the 4-wave / 128 × 128-per-wave mainloop (-2: split count unsupported)
 int gemm_dw4(const bf16* A, const bf16* B, long long T, int M, int N, int lda, int ldb, bf16* C, int ldc,
              int accumulate, bf16* ws, int splits, hipStream_t st, int variant);
+// gemm_dw4.hip, grouped: n independent problems C_i[M_i][N_i] (+)= A_iᵀ·B_i in one
+// launch per DW_GROUP_MAX problems, one workgroup per 256 × 256 output tile over the
+// whole token axis (no split-K, no partials, no fold).  The problem table travels as
+// a kernel argument.  Per-problem contract (gemm_dw4_grouped_ok): M % 128 = 0,
+// N % 256 = 0, T % 128 = 0, T ≥ 256.  Problems of one launch run concurrently: the
+// caller keeps overlapping destinations in different calls.  -2: a problem breaks
+// the contract (nothing is launched).
+constexpr int DW_GROUP_MAX = 32;
+struct DwProblem {
+  const bf16* A;  // dy [T][M], row stride lda
+  const bf16* B;  // x  [T][N], row stride ldb
+  bf16* C;        // [M][N], row stride ldc
+  long long T;
+  int M, N, lda, ldb, ldc, accumulate;
+};
+bool gemm_dw4_grouped_ok(long long T, int M, int N);
+int gemm_dw4_grouped(const DwProblem* probs, int n, hipStream_t st);
 // which mainloop gemm_dw() runs: 0 = 8-wave (gemm_dw.hip), 1.. = 4-wave variant impl - 1
 void gemm_dw_set_impl(int impl);
 int gemm_dw_get_impl();

@@ -12,6 +12,8 @@ PyTorch fp32 reference (CPU, and the oracle of the numerics tests).
 from .core import (  # noqa: F401
     _HIP_DW, _NT_ALL, _arena_grads, _direct_ok, _fwd_gemm, _input_grad, _signal_ready, _splitk, _weight_grad,
     _weight_grad_lib, _workspace, deferred_reductions, flush_deferred, linear, ref_attention, ref_bias_gelu,
+    _DW_GROUPED, _DW_CUS, _DW_CAP_BYTES, deferred_weight_grads, flush_weight_grads, dw_tiles, dw_should_flush,
+    dw_grouped_prefix,
     ref_cross_entropy, ref_layer_norm, transpose, use_hip,
     Dropout, dropout_spec, dropout_thr, philox4x32_10, philox_keep_mask, ref_dropout,
     ATTN_SITE0, attn_dropout_spec, attn_dropout_thr, philox_attn_keep_mask)
@@ -31,5 +33,6 @@ __all__ = [
     "embedding", "ref_layer_norm", "ref_bias_gelu", "ref_attention",
     "ref_cross_entropy", "use_hip", "linear", "mlp", "qkv_attention", "lm_head_xent",
     "conv_bn_act", "conv_bn_ds_act", "bn_act", "deferred_reductions",
+    "deferred_weight_grads", "flush_weight_grads",
     "Dropout", "dropout_spec", "philox_keep_mask", "attn_dropout_spec", "philox_attn_keep_mask", "ATTN_SITE0",
 ]

@@ -7,7 +7,8 @@
 * the flat-arena gradient hand-off: weight / bias / norm-weight gradients
   written or reduced straight into the parameter's arena slice
   (``_arena_grads``, ``_signal_ready``), deferred batched column sums
-  (``deferred_reductions``), the step's prebuilt Wᵀ operands (``transpose``);
+  (``deferred_reductions``), weight-gradient GEMMs grouped into whole rounds
+  (``deferred_weight_grads``), the step's prebuilt Wᵀ operands (``transpose``);
 * ``linear`` on gemm_nt4 (forward, dX) and gemm_dw4 (dW into the arena).
 
 The module-level one-element lists (``_NT_ALL``, ``_HIP_DW``, …) are test
@@ -406,11 +407,18 @@ def _weight_grad(w, dy2, x2):
         g = torch.empty(Fo, K, device=dy2.device, dtype=dy2.dtype)
         _native.require_hip().splitk_add(part, g, False)
         return g
+    if _dw_queue.push(w, dy2, x2):
+        return None  # runs, and signals, in flush_weight_grads
+    _weight_grad_now(w, dy2, x2)
+    w._pdo_ready(w)
+    return None
+
+
+def _weight_grad_now(w, dy2, x2):
+    """The arena dW of one parameter on its own launch (split-K gemm_dw, or the library)."""
     if not (_HIP_DW[0] and dy2.is_cuda and w.grad.dtype == torch.bfloat16 and dy2.is_contiguous()
             and x2.is_contiguous() and _native.require_hip().gemm_dw(dy2, x2, w.grad, True)):
         _weight_grad_lib(w, dy2, x2)
-    w._pdo_ready(w)
-    return None
 
 
 # dW on the HIP token-major GEMM (csrc/hip/gemm_dw.hip) where its shape
@@ -475,10 +483,151 @@ class deferred_reductions:
 
 
 def flush_deferred():
-    """Run the queued column sums now (stream-ordered; a no-op when none)."""
+    """Run the queued weight gradients and column sums now (stream-ordered; a
+    no-op when none)."""
+    flush_weight_grads()
     m = _native.hip_ext()
     if m is not None and m.colsum_pending():
         m.colsum_flush()
+
+
+# ----------------------------------------------------------------------------
+# grouped weight gradients
+# ----------------------------------------------------------------------------
+# Inside ``deferred_weight_grads`` (the trainer's backward) the arena dW GEMMs are
+# queued with their operands held alive and run as ONE launch per group
+# (csrc/hip/gemm_dw4.hip gemm_dw4_grouped): a workgroup owns one 256 × 256 output
+# tile over the whole token axis, so nothing is split, no partial is written and
+# nothing is folded, and a group whose tiles fill whole rounds of one workgroup
+# per CU keeps every CU busy.  A single GEMM has too few tiles for that (GPT-2-
+# medium: 48 / 16 / 64 / 64) and has to invent parallelism with split-K.
+#
+# The operands are read at the flush, later than today.  Nothing in the backward
+# writes to them in between: dy2 / x2 are saved activations or gradients that the
+# producing kernel wrote before _weight_grad was called; the residual-stream dh
+# that _LinearResFn / _NTMLPFn hand on as an alias is only read downstream
+# (layernorm_bwd_add writes a fresh tensor), autograd's in-place accumulation
+# needs a sole owner of the storage (the queue holds one more), and scale_dev_
+# runs on the LM head's dh before any consumer sees it.
+#
+# (Test hooks: _DW_GROUPED off = every dW on its own launch, as outside the scope;
+# _DW_CUS overrides the device's CU count; _DW_CAP_BYTES the held-operand cap.)
+_DW_GROUPED = [True]
+_DW_CUS = [0]
+_DW_CAP_BYTES = [16 << 30]  # GPT-2-medium's 4-layer group holds ≈ 8.6 GB of operands
+_DW_MIN_ROUNDS = 3          # a launch boundary drains the chip: whole groups of ≥ 3 rounds
+_DW_FILL = 0.94             # gemm_dw's own threshold for "the last round is nearly full"
+
+
+def dw_tiles(M: int, N: int) -> int:
+    """Output tiles (256 × 256, a half-height last row allowed) of an [M, N] dW."""
+    return ((M + 255) // 256) * (N // 256)
+
+
+def dw_should_flush(tiles, held_bytes: int, cus: int, cap_bytes: int, min_rounds: int = _DW_MIN_ROUNDS) -> bool:
+    """The flush rule after a push, a pure function of the queued tile counts:
+    flush when the tiles make whole rounds of one workgroup per CU (a positive
+    multiple of ``cus``, at least ``min_rounds`` of them), or when the held operand
+    bytes pass the cap."""
+    total = sum(tiles)
+    if total > 0 and total % cus == 0 and total >= min_rounds * cus:
+        return True
+    return held_bytes > cap_bytes
+
+
+def dw_grouped_prefix(tiles, cus: int, fill: float = _DW_FILL) -> int:
+    """How many leading queue entries a flush runs grouped: the longest prefix
+    whose last round of ``cus`` workgroups is at least ``fill`` full.  The rest (a
+    remainder that would leave CUs idle for a whole round) take the per-GEMM
+    split-K path, so no shape runs slower than on its own."""
+    best, total = 0, 0
+    for i, t in enumerate(tiles):
+        total += t
+        last = total % cus or cus
+        if total > 0 and last >= fill * cus:
+            best = i + 1
+    return best
+
+
+class _DWQueue:
+    def __init__(self):
+        self.depth = 0       # nested deferred_weight_grads scopes
+        self.entries = []    # (w, dy2, x2): the tensors stay alive until the flush
+        self.tiles = []
+        self.held = 0
+        self.cus = 0
+        self.n_grouped = 0   # problems run grouped so far (tests, probes)
+
+    def push(self, w, dy2, x2) -> bool:
+        """Queue the arena dW of ``w`` when it is within the grouped kernel's
+        contract; False = the caller runs it now."""
+        if not (self.depth and _DW_GROUPED[0] and _HIP_DW[0] and dy2.is_cuda and dy2.dtype == torch.bfloat16
+                and x2.dtype == torch.bfloat16 and w.grad.dtype == torch.bfloat16 and dy2.is_contiguous()
+                and x2.is_contiguous() and dy2.dim() == 2 and x2.dim() == 2):
+            return False
+        T, M, N = dy2.shape[0], dy2.shape[1], x2.shape[1]
+        if x2.shape[0] != T or w.grad.numel() != M * N:
+            return False
+        if not _native.require_hip().gemm_dw_grouped_ok(T, M, N):
+            return False
+        if not self.cus:
+            self.cus = _DW_CUS[0] or torch.cuda.get_device_properties(dy2.device).multi_processor_count
+        self.entries.append((w, dy2, x2))
+        self.tiles.append(dw_tiles(M, N))
+        self.held += (dy2.numel() + x2.numel()) * 2
+        if dw_should_flush(self.tiles, self.held, self.cus, _DW_CAP_BYTES[0]):
+            self.flush()
+        return True
+
+    def flush(self):
+        if not self.entries:
+            return
+        entries, tiles, cus = self.entries, self.tiles, self.cus
+        self.entries, self.tiles, self.held, self.cus = [], [], 0, 0  # a ready hook may flush again
+        k = dw_grouped_prefix(tiles, cus)
+        if k:
+            m = _native.require_hip()
+            outs = [w.grad.view(dy2.shape[1], x2.shape[1]) for w, dy2, x2 in entries[:k]]
+            if not m.gemm_dw_grouped([e[1] for e in entries[:k]], [e[2] for e in entries[:k]], outs, [True] * k):
+                raise RuntimeError("gemm_dw_grouped rejected a queued weight gradient")
+            self.n_grouped += k
+        for w, dy2, x2 in entries[k:]:
+            _weight_grad_now(w, dy2, x2)
+        for w, _, _ in entries:
+            w._pdo_ready(w)
+
+
+_dw_queue = _DWQueue()
+
+
+class deferred_weight_grads:
+    """Scope (the trainer's backward) in which the arena weight-gradient GEMMs
+    are queued and run grouped (above).  They are flushed when the queued tiles
+    fill whole rounds, when the held operands pass the cap, by
+    ``flush_deferred`` (before a bucket all-reduce) and on exit; a parameter's
+    ``_pdo_ready`` fires after the flush that ran it."""
+
+    def __init__(self, device):
+        self.on = torch.device(device).type == "cuda" and _native.ops_mode() != "torch"
+
+    def __enter__(self):
+        if self.on:
+            _dw_queue.depth += 1
+        return self
+
+    def __exit__(self, *exc):
+        if self.on:
+            _dw_queue.depth -= 1
+            if _dw_queue.depth == 0:
+                if exc and exc[0] is not None:
+                    _dw_queue.entries, _dw_queue.tiles, _dw_queue.held = [], [], 0  # a failed backward: drop, do not launch
+                else:
+                    _dw_queue.flush()
+
+
+def flush_weight_grads():
+    """Run the queued weight gradients now and signal their parameters ready."""
+    _dw_queue.flush()
 
 
 def _signal_ready(params):

@@ -19,7 +19,7 @@ import torch
 import torch.distributed as dist
 
 from .models.gpt2 import GPT2, GPT2Config
-from .ops import deferred_reductions
+from .ops import deferred_reductions, deferred_weight_grads
 from .ops.optim import FlatAdamW, cosine_lr
 from .parallel.ddp import BucketedDDP
 from .parallel.flat import FlatParams
@@ -201,7 +201,8 @@ class GPT2Trainer:
                 loss = self.model(idx, tgt)
             # bias / norm-weight column sums batched (flushed before each bucket
             # all-reduce and at the end of the backward)
-            with trace.range("backward"), deferred_reductions(self.device):
+            # (and the arena dW GEMMs grouped into whole rounds, ops.core deferred_weight_grads)
+            with trace.range("backward"), deferred_reductions(self.device), deferred_weight_grads(self.device):
                 loss.backward()
         with trace.range("allreduce_drain"):
             self.ddp.finish(self.opt if self.opt.max_grad_norm else None)
@@ -228,7 +229,8 @@ class GPT2Trainer:
                 with contextlib.nullcontext() if i == K else self.ddp.no_sync():
                     with trace.range("forward"):
                         loss = self.model(x, y)
-                    with trace.range("backward"), deferred_reductions(self.device):
+                    with trace.range("backward"), deferred_reductions(self.device), \
+                            deferred_weight_grads(self.device):
                         (loss * (1.0 / K)).backward()
                     # after finish the split LM-head slot is folded into its gradient and zero
                     with trace.range("allreduce_drain"):

@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--dropout", type=float, default=float(os.environ.get("PDO_PROBE_DROPOUT", "0")),
                     help="embedding + residual dropout probability")
     ap.add_argument("--attn-dropout", type=float, default=float(os.environ.get("PDO_PROBE_ATTN_DROPOUT", "0")))
+    ap.add_argument("--dw-grouped", type=int, default=int(os.environ.get("PDO_PROBE_DW_GROUPED", "1")),
+                    help="0: every weight-gradient GEMM on its own split-K launch (ops.core _DW_GROUPED off)")
     a = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -46,6 +48,9 @@ def main():
         dev = torch.device("cuda", 0)
         torch.cuda.set_device(dev)
     cfg = GPT2Config.named(a.model)
+    if not a.dw_grouped:
+        from paddle_operator_amd.ops import core
+        core._DW_GROUPED[0] = False
     if a.dropout or a.attn_dropout:
         cfg.embd_pdrop = cfg.resid_pdrop = a.dropout
         cfg.attn_pdrop = a.attn_dropout
