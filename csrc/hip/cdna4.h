@@ -176,5 +176,12 @@ __device__ __forceinline__ void mfma16_acc(f32x4& c, const bf16x8& a, const bf16
 __device__ __forceinline__ void mfma16_acc0(f32x4& c, const bf16x8& a, const bf16x8& b) {
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
 }
+// the same pair for v_mfma_f32_32x32x16_bf16, under the same rules (gemm_dw4)
+__device__ __forceinline__ void mfma32_acc(f32x16& c, const bf16x8& a, const bf16x8& b) {
+  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+}
+__device__ __forceinline__ void mfma32_acc0(f32x16& c, const bf16x8& a, const bf16x8& b) {
+  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
+}
 
 }  // namespace pdo

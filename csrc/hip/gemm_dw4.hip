@@ -4,21 +4,36 @@
 // by gemm_dw_set_impl).  The operand handling is gemm_dw's: token-major tiles
 // staged into LDS as they lie in memory (LDS-DMA, swizzle on the source
 // address) and every fragment read with ds_read_b64_tr_b16; the schedule is
-// gemm_nt4's (profiles/r2_gemm_nt4.md): each wave owns 128 × 128 outputs = 16
-// v_mfma_f32_32x32x16_bf16 accumulators (256 registers, pinned to the
-// accumulator file), and one instruction stream per wave interleaves MFMAs,
-// transposed reads and DMA:
+// gemm_nt4's (profiles/r2_gemm_nt4.md): each wave owns 128 × 128 outputs = 256
+// accumulator registers, pinned to the accumulator file, and one instruction
+// stream per wave interleaves MFMAs, transposed reads and DMA.
 //
-//   tile t (64 tokens, LDS buffer t&1), two barriers per tile: each 32-token
-//   half of a buffer is refilled with tile t+2 as soon as every wave has read
-//   it, so every DMA piece has ≈ 1.5 tiles of lead (hipBLASLt's gfx950 loop
-//   does the same with three barriers).
+// The schedule (dw4_tile, written once for both MFMA shapes): tile t (64 tokens,
+// LDS buffer t & 1) is two 32-token blocks of 16 MFMA groups, two barriers per
+// tile.  Each 32-token half of a buffer is refilled with tile t+2 as soon as every
+// wave has read it — the first half during block 0 of tile t (after barrier B0:
+// F0(t) reads done), the second during block 1 (after B1: F1(t) reads done).  Tile
+// t+1's data therefore has ≈ 1.5 tiles of lead (issued during tile t-1, first read
+// after B1 of tile t) instead of ≈ 0.5, at the price of two barriers per tile
+// (hipBLASLt's gfx950 loop does the same with three).
 //
 // RAW / WAR: a buffer half is refilled only after the barrier that follows
 // every wave's last read of it; a tile is read only after every wave retired
 // its own DMA of it and passed a barrier.  (Round 4 housekeeping: the
 // one-barrier schedules of round 2 measured slower and were removed,
 // profiles/r2_gemm_nt4.md.)
+//
+// The two kernels run it on the two MFMA shapes; they differ in the LDS swizzle
+// (dw_tile.h), the fragment addressing (rd), the accumulators a group touches (mma)
+// and the epilogue:
+//   gemm_dw4_kernel     v_mfma_f32_32x32x16_bf16, 4 × 4 accumulators of 32 × 32, a
+//                       block is two k-steps of 4 A + 4 B fragments (A/B alternative);
+//   gemm_dw4m16_kernel  v_mfma_f32_16x16x32_bf16, 8 × 8 accumulators of 16 × 16, a
+//                       block is ONE k-step of 8 A + 8 B fragments (the default; also
+//                       the convolution weight gradient and the grouped launch).
+// Their set-up and prologue stay written out per kernel: moved into a shared
+// forced-inline body, hipcc compiles every kernel differently
+// (profiles/r14_dw4_one_mainloop.md).
 #include <type_traits>
 
 #include "dw_tile.h"
@@ -35,6 +50,72 @@ constexpr int OPB = TILE * 2;         // bytes per operand tile (32 KiB)
 constexpr int NTHR = 256;
 using Tile = DwTile<LROW>;            // the 32x32x16 variant's swizzle and fragments (dw_tile.h)
 
+// One tile of the schedule: tile t lies in LDS buffer BUF, f0 holds its block 0
+// (tokens 0-31).  Block 0's 16 MFMA groups run while block 1 is read into f1 and, with
+// EOUT, the first half of tile t+2 is DMAed over block 0's rows; block 1's groups run
+// while (MORE) tile t+1's block 0 is read into f0 and the second half follows.
+// mma(first_tag, f, g): the shape's MFMAs of group g on fragments f; FIRST: the
+// accumulators' first write.  Pieces: first half = A 0-3, B 8-11; second = A 4-7, B 12-15.
+template <int BUF, bool MORE, bool FIRST, bool EOUT, class Srcs, class Dma, class Rd, class Mma>
+__device__ __forceinline__ void dw4_tile(int t, Srcs& srcs, Dma& dma, Rd& rd, Mma& mma, bf16x8 (&f0)[16],
+                                         bf16x8 (&f1)[16]) {
+  using NB = std::integral_constant<int, BUF ^ 1>;
+  using SB = std::integral_constant<int, BUF>;
+  decltype(srcs(0)) sn2{};
+  if constexpr (EOUT) sn2 = srcs(t + 2);
+  // B0: every wave's F0(t) reads (buffer BUF, tokens 0-31) are done
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    mma(std::bool_constant<FIRST>{}, f0, g);
+    f1[g] = rd(SB{}, 1, g);
+    if constexpr (EOUT) {
+      if (g & 1) dma(sn2, SB{}, (g >> 1) < 4 ? (g >> 1) : (g >> 1) + 4);  // first-half pieces
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // B1: every wave's F1(t) reads are done (tokens 32-63 of BUF free) and tile t+1
+  // has landed (only tile t+2's first-half pieces may still fly)
+  if constexpr (MORE || EOUT) {
+    if constexpr (EOUT)
+      asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    mma(std::false_type{}, f1, g);
+    if constexpr (MORE) f0[g] = rd(NB{}, 0, g);
+    if constexpr (EOUT) {
+      if (g & 1) dma(sn2, SB{}, (g >> 1) < 4 ? (g >> 1) + 4 : (g >> 1) + 8);  // second-half pieces
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// Workgroup → output tile (tm, tn) and split of a split-K launch, and the split's
+// k-tiles [k0, k0 + nk).  M % 256 == 128: a half-height last row of tiles.  k-tiles
+// are dealt to the splits in pairs (the mainloop runs tiles in pairs): the first
+// P % splits slices take one pair more.
+__device__ __forceinline__ void dw4_slice(int M, int N, int splits, int ksteps_total, int& tm, int& tn, int& split,
+                                          int& k0, int& nk) {
+  const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;
+  const int nwg = tiles_m * tiles_n * splits;
+  const int id = xcd_remap((int)blockIdx.x, nwg);
+  tn = id % tiles_n;
+  tm = (id / tiles_n) % tiles_m;
+  split = id / (tiles_n * tiles_m);
+  const int pq = (ksteps_total >> 1) / splits, pr = (ksteps_total >> 1) % splits;
+  k0 = 2 * (split * pq + min(split, pr));
+  nk = 2 * (pq + (split < pr ? 1 : 0));
+}
+
 __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                                                            int lda, int ldb, int M, int N, int ksteps_total,
                                                            int splits, bf16* __restrict__ C, int ldc,
@@ -43,17 +124,8 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restric
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w >> 1, wn = w & 1;
-  const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;  // M % 256 == 128: a half-height last row of tiles
-  const int nwg = tiles_m * tiles_n * splits;
-  const int id = xcd_remap((int)blockIdx.x, nwg);
-  const int tn = id % tiles_n;
-  const int tm = (id / tiles_n) % tiles_m;
-  const int split = id / (tiles_n * tiles_m);
-  // k-tiles are dealt to the splits in pairs (the mainloop runs tiles in pairs):
-  // the first P % splits slices take one pair more
-  const int pq = (ksteps_total >> 1) / splits, pr = (ksteps_total >> 1) % splits;
-  const int k0 = 2 * (split * pq + min(split, pr));
-  const int nk = 2 * (pq + (split < pr ? 1 : 0));
+  int tm, tn, split, k0, nk;
+  dw4_slice(M, N, splits, ksteps_total, tm, tn, split, k0, nk);
   const int m0 = tm * BM, n0 = tn * BN;
 
   // ---- LDS-DMA: a wave-instruction fills 1 KiB = 2 token rows of 512 B.  Wave
@@ -111,27 +183,13 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restric
       default: return Tile::frag<48>(T);
     }
   };
-  // 32x32x16 forms of cdna4.h's mfma16_acc / mfma16_acc0 (same rules)
-  auto mma = [](f32x16& c, const bf16x8& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-  };
-  auto mma0 = [](f32x16& c, const bf16x8& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
-  };
   using B0 = std::integral_constant<int, 0>;
   using B1 = std::integral_constant<int, 1>;
 
-  f32x16 acc[4][4];  // first written by mma0 in tile 0's block 0
+  f32x16 acc[4][4];  // first written with FIRST in tile 0's block 0
   bf16x8 f0[16], f1[16];
 
   {
-    // ---- half-buffer refill schedule: each 32-token half of a buffer is
-    // refilled as soon as every wave has read it — tile t+2's first half during
-    // block 0 of tile t (after barrier B0: F0(t) reads done), its second half during
-    // block 1 (after B1: F1(t) reads done).  Tile t+1's data therefore has ≈1.5 tiles
-    // of lead (issued during tile t-1, first read after B1 of tile t) instead of ≈0.5,
-    // at the price of two barriers per tile (hipBLASLt's gfx950 loop does the same
-    // with three).  Pieces: first half = A 0-3, B 8-11; second half = A 4-7, B 12-15.
     {
       const Src s0 = srcs(0), s1 = srcs(1);
 #pragma unroll
@@ -145,56 +203,19 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restric
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < 16; ++q) f0[q] = rd(B0{}, 0, q);
-    auto tileH = [&](int t, auto buf_tag, auto more_tag, auto first_tag, auto eout_tag) {
-      constexpr int BUF = decltype(buf_tag)::value;
-      constexpr bool MORE = decltype(more_tag)::value;
+    auto mma = [&](auto first_tag, const bf16x8* f, int g) {
+      // group g: k-step g >> 3, A fragment (g >> 1) & 3 against B fragments 2(g & 1), +1
       constexpr bool FIRST = decltype(first_tag)::value;
-      constexpr bool EOUT = decltype(eout_tag)::value;
-      using NB = std::integral_constant<int, BUF ^ 1>;
-      using SB = std::integral_constant<int, BUF>;
-      Src sn2{};
-      if constexpr (EOUT) sn2 = srcs(t + 2);
-      // B0: every wave's F0(t) reads (buffer BUF, tokens 0-31) are done
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
+      const int ks = g >> 3, mb = (g >> 1) & 3, nb0 = 2 * (g & 1);
 #pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        const int ks = g >> 3, mb = (g >> 1) & 3, nb0 = 2 * (g & 1);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          if (FIRST && ks == 0) mma0(acc[mb][nb0 + u], f0[8 * ks + mb], f0[8 * ks + 4 + nb0 + u]);
-          else mma(acc[mb][nb0 + u], f0[8 * ks + mb], f0[8 * ks + 4 + nb0 + u]);
-        }
-        f1[g] = rd(buf_tag, 1, g);
-        if constexpr (EOUT) {
-          if (g & 1) dma(sn2, SB{}, (g >> 1) < 4 ? (g >> 1) : (g >> 1) + 4);  // first-half pieces
-        }
-        __builtin_amdgcn_sched_barrier(0);
+      for (int u = 0; u < 2; ++u) {
+        if (FIRST && ks == 0) mfma32_acc0(acc[mb][nb0 + u], f[8 * ks + mb], f[8 * ks + 4 + nb0 + u]);
+        else mfma32_acc(acc[mb][nb0 + u], f[8 * ks + mb], f[8 * ks + 4 + nb0 + u]);
       }
-      // B1: every wave's F1(t) reads are done (tokens 32-63 of BUF free) and tile t+1
-      // has landed (only tile t+2's first-half pieces may still fly)
-      if constexpr (MORE || EOUT) {
-        if constexpr (EOUT)
-          asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-        else
-          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        const int ks = g >> 3, mb = (g >> 1) & 3, nb0 = 2 * (g & 1);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) mma(acc[mb][nb0 + u], f1[8 * ks + mb], f1[8 * ks + 4 + nb0 + u]);
-        if constexpr (MORE) f0[g] = rd(NB{}, 0, g);
-        if constexpr (EOUT) {
-          if (g & 1) dma(sn2, SB{}, (g >> 1) < 4 ? (g >> 1) + 4 : (g >> 1) + 8);  // second-half pieces
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
+    };
+    auto tileH = [&](int t, auto buf_tag, auto more_tag, auto first_tag, auto eout_tag) {
+      dw4_tile<decltype(buf_tag)::value, decltype(more_tag)::value, decltype(first_tag)::value,
+               decltype(eout_tag)::value>(t, srcs, dma, rd, mma, f0, f1);
     };
     using T_ = std::true_type;
     using F_ = std::false_type;
@@ -243,26 +264,10 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4_kernel(const bf16* __restric
 // clock on the 16x16x32 shape — MI355X_MICROARCH.md 'DVFS give-back' item 7
 // (1.12-1.15x FLOP/s at equal cycles per FLOP in LDS-fed loops).
 //
-// Fragment: lane group g = l >> 4 reads 4 token rows 4g .. 4g+3 (lo) and
-// 16 + 4g .. (hi) of the 16 columns cb .. cb+15 with ds_read_b64_tr_b16, so lane
-// l holds column cb + (l & 15) at tokens {4g..4g+3, 16+4g..16+4g+3} — a k
-// permutation shared by both operands.  The 16 rows a wave reads per
-// instruction pair up as lane groups {0,1} / {2,3} (or {0,2} / {1,3}); with the
-// 32x32 swizzle rows r and r + 4 would hit the same banks, so this tile's
-// swizzle XORs the 32-B column pair index with (r & 3) | bit2 = b2(r) ^ b3(r):
-// 8 distinct bank octets for either pairing.  The DMA's source-side swizzle
-// then depends on the piece's parity (row bit 3): two per-lane offsets per operand.
-__device__ __forceinline__ int swz16(int r) { return ((r & 3) | ((((r >> 2) ^ (r >> 3)) & 1) << 2)) << 1; }
-__device__ __forceinline__ int loff16(int r, int ch) { return r * LROW + ((ch ^ swz16(r)) << 3); }
-__device__ __forceinline__ int frag_base16(int cb, int lane) {
-  const int g = lane >> 4, t = lane & 15, q = t >> 2, p = t & 3;
-  const int col = cb + 4 * p;
-  return loff16(4 * g + q, col >> 3) + (col & 7);
-}
-template <int K0>
-__device__ __forceinline__ bf16x8 frag16(const bf16* T) {
-  return ld_tr8(T + K0 * LROW, T + (K0 + 16) * LROW);
-}
+// The tile swizzle and fragment layout of this shape: dw_tile.h (DwTile16); the DMA's
+// source-side swizzle depends on the piece's parity (row bit 3): two per-lane offsets
+// per operand.
+using Tile16 = DwTile16<LROW>;  // this shape's swizzle and fragments (dw_tile.h)
 
 // GATHER (the convolution weight gradient, conv.hip's conv_wgrad): B is not a
 // token-major matrix but the NHWC activation gathered per tap — column
@@ -350,27 +355,19 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(
     dw_group_mn(g - tb.first[pi], (M + BM - 1) / BM, N / BN, tm, tn);
     split = 0, k0 = 0, nk = e.ksteps;
   } else {
-    const int tiles_n = N / BN, tiles_m = (M + BM - 1) / BM;
-    const int nwg = tiles_m * tiles_n * splits;
-    const int id = xcd_remap((int)blockIdx.x, nwg);
-    tn = id % tiles_n;
-    tm = (id / tiles_n) % tiles_m;
-    split = id / (tiles_n * tiles_m);
-    const int pq = (ksteps_total >> 1) / splits, pr = (ksteps_total >> 1) % splits;
-    k0 = 2 * (split * pq + min(split, pr));
-    nk = 2 * (pq + (split < pr ? 1 : 0));
+    dw4_slice(M, N, splits, ksteps_total, tm, tn, split, k0, nk);
   }
   const int m0 = tm * BM, n0 = tn * BN;
 
   // LDS-DMA: piece i of an operand = rows 8i + 2w + rl (rl = l >> 5), LDS chunk
-  // l & 31 ← global chunk (l & 31) ^ swz16(row); swz16 of that row is fixed per
+  // l & 31 ← global chunk (l & 31) ^ Tile16::swz(row); the swizzle of that row is fixed per
   // lane up to the piece parity (row bit 3 = i & 1)
   const int rl = lane >> 5, rw = 2 * w + rl;
   unsigned voffA[2], voffB[2];
 #pragma unroll
   for (int par = 0; par < 2; ++par) {
-    const int cs = (lane & 31) ^ swz16(8 * par + rw);
-    const int csa = (m0 + BM > M && cs >= 16) ? cs - 16 : cs;  // half-height edge tile (as gemm_dw4_kernel)
+    const int cs = (lane & 31) ^ Tile16::swz(8 * par + rw);
+    const int csa = (m0 + BM > M && cs >= 16) ? cs - 16 : cs;  // half-height edge tile (see gemm_dw4_kernel)
     voffA[par] = (unsigned)((rl * lda + csa * 8) * 2);
     voffB[par] = (unsigned)((rl * ldb + cs * 8) * 2);
   }
@@ -384,7 +381,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(
   if constexpr (GATHER) {
 #pragma unroll
     for (int par = 0; par < 2; ++par) {
-      const int col = n0 + (((lane & 31) ^ swz16(8 * par + rw)) << 3);
+      const int col = n0 + (((lane & 31) ^ Tile16::swz(8 * par + rw)) << 3);
       const int tap = col / gx.C, r = tap / gx.S;
       gci[par] = col - tap * gx.C;
       gdh[par] = col < gx.TC ? r - gx.pad : -(1 << 20);  // a padding column fails every bounds check
@@ -430,18 +427,18 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(
   int fo[16];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    fo[i] = frag_base16(wm * 128 + 16 * i, lane);
-    fo[8 + i] = TILE + frag_base16(wn * 128 + 16 * i, lane);
+    fo[i] = Tile16::frag_base(wm * 128 + 16 * i, lane);
+    fo[8 + i] = TILE + Tile16::frag_base(wn * 128 + 16 * i, lane);
   }
   auto rd = [&](auto buf_tag, int h, int q) -> bf16x8 {
     constexpr int BUF = decltype(buf_tag)::value;
     const bf16* T = smA[BUF] + fo[q];
-    return h ? frag16<32>(T) : frag16<0>(T);
+    return h ? Tile16::frag<32>(T) : Tile16::frag<0>(T);
   };
   using B0 = std::integral_constant<int, 0>;
   using B1 = std::integral_constant<int, 1>;
 
-  f32x4 acc[8][8];  // first written by mma0 in tile 0's block 0
+  f32x4 acc[8][8];  // first written with FIRST in tile 0's block 0
   bf16x8 f0[16], f1[16];
 
   {
@@ -457,59 +454,21 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int q = 0; q < 16; ++q) f0[q] = rd(B0{}, 0, q);
-  // group g of a block: A fragment g >> 1 against B fragments 4(g & 1) .. +3
-  auto tileH = [&](int t, auto buf_tag, auto more_tag, auto first_tag, auto eout_tag) {
-    constexpr int BUF = decltype(buf_tag)::value;
-    constexpr bool MORE = decltype(more_tag)::value;
+  auto mma = [&](auto first_tag, const bf16x8* f, int g) {
+    // group g: A fragment g >> 1 against B fragments 4(g & 1) .. +3
     constexpr bool FIRST = decltype(first_tag)::value;
-    constexpr bool EOUT = decltype(eout_tag)::value;
-    using NB = std::integral_constant<int, BUF ^ 1>;
-    using SB = std::integral_constant<int, BUF>;
-    Src sn2{};
-    if constexpr (EOUT) sn2 = srcs(t + 2);
-    // B0: every wave's F0(t) reads (tokens 0-31 of BUF) are done
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    const int mb = g >> 1, nb0 = 4 * (g & 1);
 #pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const int mb = g >> 1, nb0 = 4 * (g & 1);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const bf16x8& fr = f0[SWAP ? 8 + nb0 + u : mb];
-        const bf16x8& fc = f0[SWAP ? mb : 8 + nb0 + u];
-        if (FIRST) mfma16_acc0(acc[mb][nb0 + u], fr, fc);
-        else mfma16_acc(acc[mb][nb0 + u], fr, fc);
-      }
-      f1[g] = rd(buf_tag, 1, g);
-      if constexpr (EOUT) {
-        if (g & 1) dma(sn2, SB{}, (g >> 1) < 4 ? (g >> 1) : (g >> 1) + 4);  // first-half pieces
-      }
-      __builtin_amdgcn_sched_barrier(0);
+    for (int u = 0; u < 4; ++u) {
+      const bf16x8& fr = f[SWAP ? 8 + nb0 + u : mb];
+      const bf16x8& fc = f[SWAP ? mb : 8 + nb0 + u];
+      if (FIRST) mfma16_acc0(acc[mb][nb0 + u], fr, fc);
+      else mfma16_acc(acc[mb][nb0 + u], fr, fc);
     }
-    // B1: every wave's F1(t) reads are done and tile t+1 has landed
-    if constexpr (MORE || EOUT) {
-      if constexpr (EOUT)
-        asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const int mb = g >> 1, nb0 = 4 * (g & 1);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        mfma16_acc(acc[mb][nb0 + u], f1[SWAP ? 8 + nb0 + u : mb], f1[SWAP ? mb : 8 + nb0 + u]);
-      if constexpr (MORE) f0[g] = rd(NB{}, 0, g);
-      if constexpr (EOUT) {
-        if (g & 1) dma(sn2, SB{}, (g >> 1) < 4 ? (g >> 1) + 4 : (g >> 1) + 8);  // second-half pieces
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+  };
+  auto tileH = [&](int t, auto buf_tag, auto more_tag, auto first_tag, auto eout_tag) {
+    dw4_tile<decltype(buf_tag)::value, decltype(more_tag)::value, decltype(first_tag)::value,
+             decltype(eout_tag)::value>(t, srcs, dma, rd, mma, f0, f1);
   };
   using T_ = std::true_type;
   using F_ = std::false_type;
@@ -603,15 +562,43 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_dw4m16_kernel(
 
 }  // namespace
 
-// every slice gets ≥ 2 pairs of k-tiles (uneven splits allowed: pairs are dealt
-// out); returns -2 when a slice would be shorter
+// The slice contract of the mainloop, stated once: k-tiles (64 tokens) run in pairs
+// and are dealt to the slices in pairs, the remainder to the first slices, and
+// every slice needs ≥ 2 pairs (the prologue fills two tiles, the tail of the loop
+// drains two).  Returns the most slices ks k-tiles can be cut into; 0 where not
+// even one slice holds (ks odd or < 4).
+static long long dw4_max_slices(long long ks) { return ks % 2 ? 0 : ks / 4; }
+
+// Split count of gemm_dw's automatic choice for this mainloop (0: none fits the
+// contract): ≤ 256 workgroups (one resident round, one workgroup per CU) unless the
+// tiles alone exceed it
+int dw4_splits(long long T, int M, int N) {
+  const int tiles = ((M + BM - 1) / BM) * (N / BN);
+  const long long ks = T / BK;
+  if (tiles > 256) {
+    // several rounds of one workgroup per CU: the smallest split whose last round
+    // is nearly full (LM head, 788 tiles: 1 slice = 3.08 rounds in 4, 4 slices = 12.3 in 13)
+    for (int s = 1; s <= 8; ++s) {
+      if (s > dw4_max_slices(ks)) continue;
+      const long long wg = (long long)tiles * s, rounds = (wg + 255) / 256;
+      if (wg * 100 >= rounds * 256 * 94) return s;
+    }
+  }
+  // the most slices that keep one resident round (≤ 256 workgroups): qkv's 48 tiles
+  // take 5 uneven slices (240 workgroups) instead of 4 even ones (192)
+  for (int s = 16; s >= 1; --s) {
+    if ((long long)tiles * s > 256 && s > 1) continue;
+    if (s <= dw4_max_slices(ks)) return s;
+  }
+  return 0;
+}
+
+// returns -2 when a slice would break the contract (uneven splits allowed)
 int gemm_dw4(const bf16* A, const bf16* B, long long T, int M, int N, int lda, int ldb, bf16* C, int ldc,
              int accumulate, bf16* ws, int splits, hipStream_t st, int variant) {
   if (M % (BM / 2) || N % BN || T % BK || splits < 1 || splits > 16) return -2;
   const long long ks = T / BK;
-  if (ks > 0x7fffffffLL) return -2;
-  // every split's k-tile count even and ≥ 4 (pairs dealt out, remainder to the first slices)
-  if (ks % 2 || (ks / 2) / splits < 2) return -2;
+  if (ks > 0x7fffffffLL || splits > dw4_max_slices(ks)) return -2;
   const int tiles = ((M + BM - 1) / BM) * (N / BN);
   const int grid = tiles * splits;
   bf16* out = C;
@@ -634,8 +621,9 @@ int gemm_dw4(const bf16* A, const bf16* B, long long T, int M, int N, int lda, i
   return 0;
 }
 
+// each problem is one slice
 bool gemm_dw4_grouped_ok(long long T, int M, int N) {
-  return M > 0 && N > 0 && M % (BM / 2) == 0 && N % BN == 0 && T % (2 * BK) == 0 && T >= 4 * BK &&
+  return M > 0 && N > 0 && M % (BM / 2) == 0 && N % BN == 0 && T % BK == 0 && dw4_max_slices(T / BK) >= 1 &&
          T / BK <= 0x7fffffffLL;
 }
 
@@ -673,19 +661,21 @@ int gemm_dw4_grouped(const DwProblem* probs, int n, hipStream_t st) {
 // Convolution weight gradient on the gathered mainloop: dW [Kout][R·S·C] fp32
 // partials per token slice into part ([splits][Kout][TCp], TCp = R·S·C rounded up
 // to 256 columns); the caller folds them.  Contract: Kout % 128 = 0, C % 8 = 0,
-// tokens % 128 = 0 with ≥ 4 64-token k-tiles per slice (pairs dealt out).
+// tokens % 64 = 0 and the slice contract above.
 int conv_wgrad_dw4_splits(int Kout, int TC, long long M) {
   const long long tiles = (long long)((Kout + 255) / 256) * ((TC + 255) / 256);
-  const long long pairs = M / 128;
   static const int ncu = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       n = 256;
     return n > 0 ? n : 256;
   }();
-  // one workgroup per CU (128 KiB of LDS each) and no second round: ⌊CUs / tiles⌋
+  // one workgroup per CU (128 KiB of LDS each) and no second round: ⌊CUs / tiles⌋,
+  // and no more than the slice contract allows
+  const long long ks = M / (2 * BK) * 2;  // whole pairs of k-tiles only
+  const long long cap = dw4_max_slices(ks);
   long long sp = ncu / tiles;
-  if (sp > pairs / 2) sp = pairs / 2;
+  if (sp > cap) sp = cap;
   if (sp > 256) sp = 256;
   return sp < 1 ? 1 : (int)sp;
 }
@@ -695,9 +685,9 @@ int conv_wgrad_dw4(const bf16* dy, const bf16* x, int N, int H, int W, int C, in
   const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
   const long long M = (long long)N * Ho * Wo;
   const int TC = R * S * C, TCp = (TC + BN - 1) / BN * BN;
-  if (Kout % (BM / 2) || C % 8 || M % (2 * BK) || M >= (1LL << 31)) return -2;
+  if (Kout % (BM / 2) || C % 8 || M % BK || M >= (1LL << 31)) return -2;
   const long long ks = M / BK;
-  if (splits < 1 || (ks / 2) / splits < 2) return -2;
+  if (splits < 1 || splits > dw4_max_slices(ks)) return -2;
   if ((long long)N * H * W * C * 2 >= (1LL << 31)) return -2;
   DwGather g{x, (unsigned)((long long)N * H * W * C * 2), C, S, H, W, Ho, Wo, TC, 1.f / (float)Ho, 1.f / (float)Wo,
              stride, pad, part};

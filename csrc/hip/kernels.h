@@ -168,6 +168,8 @@ int gemm_dw(const bf16* A, const bf16* B, long long T, int M, int N, int lda, in
 // gemm_dw4.hip: the same contract on the 4-wave / 128 × 128-per-wave mainloop (-2: split count unsupported)
 int gemm_dw4(const bf16* A, const bf16* B, long long T, int M, int N, int lda, int ldb, bf16* C, int ldc,
              int accumulate, bf16* ws, int splits, hipStream_t st, int variant);
+// gemm_dw_splits' choice for that mainloop (0: no split count fits its slice contract)
+int dw4_splits(long long T, int M, int N);
 // gemm_dw4.hip, grouped: n independent problems C_i[M_i][N_i] (+)= A_iᵀ·B_i in one
 // launch per DW_GROUP_MAX problems, one workgroup per 256 × 256 output tile over the
 // whole token axis (no split-K, no partials, no fold).  The problem table travels as
