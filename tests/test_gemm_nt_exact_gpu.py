@@ -174,14 +174,17 @@ def rne_bf16(v):
     return as_bf16(rne(v))
 
 
-def classify(v, delta=DELTA, floor=BAND_FLOOR):
+def classify(v, delta=DELTA, floor=BAND_FLOOR, band=None):
     """(lo, hi, near, ambiguous) of float64 v: its two bf16 neighbours (equal where v is
     representable), RNE(v), and whether v lies within delta * max(|v|, floor) of the midpoint of
-    lo and hi (never where v is representable: the next midpoints are half a spacing away)."""
+    lo and hi (never where v is representable: the next midpoints are half a spacing away).
+    band (optional): a float64 tensor of absolute half-widths per element, used instead of
+    delta * max(|v|, floor)."""
     q = _quantum(v)
     lo, hi = torch.floor(v / q) * q, torch.ceil(v / q) * q
     near = torch.round(v / q) * q
-    amb = (lo != hi) & ((v - (lo + hi) * 0.5).abs() <= delta * v.abs().clamp_min(floor))
+    width = delta * v.abs().clamp_min(floor) if band is None else band
+    amb = (lo != hi) & ((v - (lo + hi) * 0.5).abs() <= width)
     return lo, hi, near, amb
 
 
