@@ -8,6 +8,7 @@
 
 #include <cmath>
 
+#include "gemm_nt_epi.h"
 #include "kernels.h"
 
 namespace {
@@ -511,10 +512,18 @@ static void nt_check(const at::Tensor& a, const at::Tensor& b) {
   TORCH_CHECK(gemm_nt_supported(a.size(0), b.size(0), a.size(1)), "gemm_nt: M, N % 256 and K % 64 required");
 }
 
+// every binding's launch: contiguous a [M, K], b [N, K], c and y [M, N]; bias, y and part as the epilogue needs them
+static void nt_run(const at::Tensor& a, const at::Tensor& b, const at::Tensor& c, int epi, const bf16* bias, bf16* y,
+                   float* part, const char* what) {
+  const int M = a.size(0), N = b.size(0), K = a.size(1);
+  const int rc = pdo::gemm_nt(bp(a), bp(b), M, N, K, K, K, bp(c), N, epi, bias, y, y ? N : 0, part, cur_stream());
+  TORCH_CHECK(rc == 0, what, " rejected the shape (code ", rc, ")");  // CHECK_RC's text
+}
+
 // c = a·bᵀ (+ bias); into `out` ([M, N] contiguous bf16) when given
 at::Tensor gemm_nt(at::Tensor a, at::Tensor b, c10::optional<at::Tensor> bias, c10::optional<at::Tensor> out) {
   nt_check(a, b);
-  const int M = a.size(0), N = b.size(0), K = a.size(1);
+  const int M = a.size(0), N = b.size(0);
   at::Tensor c;
   if (out.has_value()) {
     CHECK_IN((*out)); CHECK_BF16((*out));
@@ -528,18 +537,16 @@ at::Tensor gemm_nt(at::Tensor a, at::Tensor b, c10::optional<at::Tensor> bias, c
     CHECK_IN((*bias)); CHECK_BF16((*bias)); TORCH_CHECK(bias->numel() == N);
     bptr = bp(*bias);
   }
-  CHECK_RC(pdo::gemm_nt(bp(a), bp(b), M, N, K, K, K, bp(c), N, bptr ? 1 : 0, bptr, nullptr, 0, nullptr,
-                        cur_stream()), "gemm_nt");
+  nt_run(a, b, c, bptr ? pdo::EPI_BIAS : pdo::EPI_PLAIN, bptr, nullptr, nullptr, "gemm_nt");
   return c;
 }
 
-// c = a·bᵀ + r (r: [M, N] contiguous bf16), one pass
-// c = a·bᵀ (+ bias) + r, one rounding on the 4-wave mainloop
+// c = a·bᵀ (+ bias) + r (r: [M, N] contiguous bf16), one pass; one rounding on the 4-wave mainloop
 at::Tensor gemm_nt_add(at::Tensor a, at::Tensor b, at::Tensor r, c10::optional<at::Tensor> bias,
                        c10::optional<at::Tensor> mask) {
   nt_check(a, b);
   CHECK_IN(r); CHECK_BF16(r);
-  const int M = a.size(0), N = b.size(0), K = a.size(1);
+  const int M = a.size(0), N = b.size(0);
   TORCH_CHECK(r.dim() == 2 && r.size(0) == M && r.size(1) == N, "gemm_nt_add: r must be [M, N]");
   const bf16* bptr = nullptr;
   if (bias && bias->defined()) {
@@ -547,17 +554,16 @@ at::Tensor gemm_nt_add(at::Tensor a, at::Tensor b, at::Tensor r, c10::optional<a
     TORCH_CHECK(bias->numel() == N, "gemm_nt_add: bias must have N elements");
     bptr = bp(*bias);
   }
-  int epi = bptr ? 5 : 4;
+  int epi = bptr ? pdo::EPI_BIAS_ADD : pdo::EPI_ADD;
   if (mask && mask->defined()) {  // c = a·bᵀ + r ⊙ keep (bit j of byte i keeps element 8i + j of r)
     TORCH_CHECK(!bptr, "gemm_nt_add: bias and mask are exclusive");
     TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == at::kByte && mask->is_contiguous() &&
                 mask->numel() == (int64_t)M * N / 8 && N % 8 == 0, "gemm_nt_add: mask [M·N/8] uint8");
     bptr = reinterpret_cast<const bf16*>(mask->data_ptr<uint8_t>());
-    epi = 6;
+    epi = pdo::EPI_ADD_MASKED;
   }
   auto c = at::empty({M, N}, a.options());
-  CHECK_RC(pdo::gemm_nt(bp(a), bp(b), M, N, K, K, K, bp(c), N, epi, bptr, bp(r), N, nullptr, cur_stream()),
-           "gemm_nt_add");
+  nt_run(a, b, c, epi, bptr, bp(r), nullptr, "gemm_nt_add");
   return c;
 }
 
@@ -570,29 +576,26 @@ std::vector<at::Tensor> gemm_nt_stats(at::Tensor a, at::Tensor b) {
   TORCH_CHECK(N % 256 == 0 || pdo::gemm_nt_epi_ok(M, N, K), "gemm_nt_stats: N % 256 = 0 on the 8-wave ring");
   auto c = at::empty({M, N}, a.options());
   auto part = at::empty({M / pdo::gemm_nt_stats_rows(K), 2, N}, a.options().dtype(at::kFloat));
-  CHECK_RC(pdo::gemm_nt(bp(a), bp(b), M, N, K, K, K, bp(c), N, 9, nullptr, nullptr, 0, fp(part), cur_stream()),
-           "gemm_nt_stats");
+  nt_run(a, b, c, pdo::EPI_STATS, nullptr, nullptr, fp(part), "gemm_nt_stats");
   return {c, part};
 }
 
 // (pre, y): pre = a·bᵀ, y = gelu(pre + bias); saved_grad: pre = gelu'(a·bᵀ + bias)
-// instead (EPI 7, for gemm_nt_dgelu(..., saved_grad=true))
+// instead (EPI_GELU_SAVE_GRAD, for gemm_nt_dgelu(..., saved_grad=true))
 std::vector<at::Tensor> gemm_nt_gelu(at::Tensor a, at::Tensor b, at::Tensor bias, bool saved_grad) {
   nt_check(a, b);
   CHECK_IN(bias); CHECK_BF16(bias);
-  const int M = a.size(0), N = b.size(0), K = a.size(1);
+  const int M = a.size(0), N = b.size(0);
   TORCH_CHECK(bias.numel() == N);
   auto pre = at::empty({M, N}, a.options());
   auto y = at::empty({M, N}, a.options());
-  CHECK_RC(pdo::gemm_nt(bp(a), bp(b), M, N, K, K, K, bp(pre), N, saved_grad ? 7 : 2, bp(bias), bp(y), N, nullptr,
-                        cur_stream()),
-           "gemm_nt_gelu");
+  nt_run(a, b, pre, saved_grad ? pdo::EPI_GELU_SAVE_GRAD : pdo::EPI_GELU, bp(bias), bp(y), nullptr, "gemm_nt_gelu");
   return {pre, y};
 }
 
 // dx = (a·bᵀ) ⊙ gelu'(pre + bias); db = colsum(dx) (accumulated into db_out when given).
 // saved_grad: pre is gemm_nt_gelu(..., saved_grad=true)'s gelu' and dx = (a·bᵀ) ⊙ pre
-// (EPI 8; bias unused)
+// (EPI_DGELU_SAVED; bias unused)
 std::vector<at::Tensor> gemm_nt_dgelu(at::Tensor a, at::Tensor b, at::Tensor pre, at::Tensor bias,
                                       c10::optional<at::Tensor> db_out, bool saved_grad) {
   nt_check(a, b);
@@ -602,9 +605,7 @@ std::vector<at::Tensor> gemm_nt_dgelu(at::Tensor a, at::Tensor b, at::Tensor pre
   auto dx = at::empty({M, N}, a.options());
   const int G = pdo::gemm_nt_dbias_rows(M, K);
   auto part = at::empty({(int64_t)G * N + pdo::colsum_scratch_floats(G, N)}, a.options().dtype(at::kFloat));
-  CHECK_RC(pdo::gemm_nt(bp(a), bp(b), M, N, K, K, K, bp(dx), N, saved_grad ? 8 : 3, bp(bias), bp(pre), N, fp(part),
-                        cur_stream()),
-           "gemm_nt_dgelu");
+  nt_run(a, b, dx, saved_grad ? pdo::EPI_DGELU_SAVED : pdo::EPI_DGELU, bp(bias), bp(pre), fp(part), "gemm_nt_dgelu");
   at::Tensor db;
   pdo::ColOut co;
   if (db_out.has_value()) {
@@ -1486,7 +1487,7 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.def("gemm_nt_supported", &gemm_nt_supported);
   m.def("gemm_nt_stats", &gemm_nt_stats);
   m.def("gemm_nt_stats_rows", [](int64_t K) { return pdo::gemm_nt_stats_rows((int)K); });
-  // EPI 7 / 8 (the saved-GELU' pair) run on the 4-wave mainloop only
+  // EPI_GELU_SAVE_GRAD / EPI_DGELU_SAVED (the saved-GELU' pair) run on the 4-wave mainloop only
   m.def("gemm_nt_epi_ok", [](int64_t M, int64_t N, int64_t K) {
     return M < (1LL << 31) && N < (1LL << 31) && pdo::gemm_nt_epi_ok((int)M, (int)N, (int)K) != 0;
   });

@@ -25,28 +25,30 @@
 //              through Y), and fp32 column partial sums of C for the bias
 //              gradient (one row per (M-tile, wave)) — the fc2 input-gradient
 //              GEMM with the bias-GELU backward pass fused
-//   EPI_ADD    C = A·Bᵀ + Y (EPI 5: + bias too — a projection writing the residual
+//   EPI_ADD    C = A·Bᵀ + Y (EPI_BIAS_ADD: + bias too — a projection writing the residual
 //              stream x + proj(a) + b) — or an input gradient that joins another branch's
 //              (ResNet's block input: conv1 dX + the identity / downsample dX);
-//              EPI 6: + Y ⊙ keep bits (a ReLU mask)
-//   EPI 7 / 8  (4-wave mainloop only) the GELU pair with the derivative saved:
-//              fc1 writes C = gelu'(A·Bᵀ + bias), Y = gelu(A·Bᵀ + bias); fc2's
+//              EPI_ADD_MASKED: + Y ⊙ keep bits (a ReLU mask, its bytes passed as `bias`)
+//   EPI_GELU_SAVE_GRAD / EPI_DGELU_SAVED  (4-wave mainloop only) the GELU pair with the
+//              derivative saved: fc1 writes C = gelu'(A·Bᵀ + bias), Y = gelu(A·Bᵀ + bias); fc2's
 //              input gradient is then C = (A·Bᵀ) ⊙ Y plus the bias-gradient
 //              partials — one multiply per element instead of the derivative
-//   EPI 9      C = A·Bᵀ and the BatchNorm statistics of the bf16 outputs per
+//   EPI_STATS  C = A·Bᵀ and the BatchNorm statistics of the bf16 outputs per
 //              row group: [groups][2][N] (Σ, Σ(x − x̄)²), gemm_nt_stats_rows
 //              rows each, merged by batchnorm.hip bn_fwd_tiles — a 1×1
 //              convolution's forward without a statistics pass over its output
+// gemm_nt_epi.h names them and states, once, what each needs and writes.
 // Rounding, this kernel (the 8-wave ring): as the unfused path bit for bit — the
-// GEMM result (+ bias for EPI 1 / 5) is rounded to bf16 when it is staged in
-// LDS, and GELU, GELU' or the addend of EPI 4 / 5 / 6 then work on that bf16
-// value, as when it made an HBM round trip (two roundings for EPI 4 / 5 / 6).
+// GEMM result (+ bias for EPI_BIAS / EPI_BIAS_ADD) is rounded to bf16 when it is staged in
+// LDS, and GELU, GELU' or the addend of the three EPI_*ADD* then work on that bf16
+// value, as when it made an HBM round trip (two roundings for the addends).
 // The 4-wave mainloop (gemm_nt4.hip) applies them to the fp32 product instead:
-// one rounding; only C of EPI 2 / 9 is the same RNE(A·Bᵀ) on both.  Both
+// one rounding; only C of EPI_GELU / EPI_STATS is the same RNE(A·Bᵀ) on both.  Both
 // contracts are pinned bit for bit by tests/test_gemm_nt_exact_gpu.py.
 #include <stdlib.h>
 
 #include "cdna4.h"
+#include "gemm_nt_epi.h"
 #include "kernels.h"
 
 namespace pdo {
@@ -57,6 +59,9 @@ constexpr int BM = 256, BN = 256, BK = 32;
 constexpr int STAGES = 5;  // 5 × 32 KiB = the whole 160 KiB LDS
 constexpr int TILE = 256 * BK;  // elements of one operand tile [256 rows][32]
 constexpr int NTHR = 512;
+// partial rows per 256-row tile: EPI_DGELU's bias gradient leaves one per wave, EPI_STATS one for the whole tile
+// (the kernel's index expressions and gemm_nt_dbias_rows / gemm_nt_stats_rows below read these)
+constexpr int DBIAS_PER_TILE = NTHR / 64, STATS_PER_TILE = 1;
 
 // 16-B chunk swizzle of a 64-B LDS row: a ds_read_b128 lane group reads the
 // 4 chunks of 4 rows ({0-3,12-15,20-27}-style groups); chunk ^= (r>>1)&3 puts
@@ -68,6 +73,7 @@ __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(const bf16* __restrict__ 
                                                        int lda, int ldb, int M, int N, int nk, bf16* __restrict__ C,
                                                        int ldc, const bf16* __restrict__ bias, bf16* __restrict__ Y,
                                                        int ldy, float* __restrict__ dbias_part) {
+  static_assert(epi_known(EPI) && !epi_nt4_only(EPI), "no such epilogue on the 8-wave ring");
   __shared__ __attribute__((aligned(16))) bf16 smem[STAGES * 2 * TILE];  // [stage][A|B][256][32]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wm = w >> 2, wn = w & 3;
@@ -176,7 +182,7 @@ __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(const bf16* __restrict__ 
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (EPI == 1 || EPI == 5) {  // bias before the rounding, as a library bias epilogue
+    if constexpr (epi_bias_into_c(EPI)) {  // bias before the rounding, as a library bias epilogue
       const bf16x4 b4 = *reinterpret_cast<const bf16x4*>(bias + n0 + wn * 64 + 16 * j + 4 * (lane >> 4));
       bv = f32x4{(float)b4[0], (float)b4[1], (float)b4[2], (float)b4[3]};
     }
@@ -194,42 +200,42 @@ __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(const bf16* __restrict__ 
   const int c = tid & 31, r0 = tid >> 5;
   const int n = n0 + 8 * c;
   f32x8 bv8;
-  if constexpr (EPI == 2 || EPI == 3) bv8 = to_f32(*reinterpret_cast<const bf16x8*>(bias + n));
+  if constexpr (epi_bias_into_activation(EPI)) bv8 = to_f32(*reinterpret_cast<const bf16x8*>(bias + n));
   f32x8 colp = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  // EPI 9: statistics of this thread's 16 rows, shifted by its first row
+  // EPI_STATS: statistics of this thread's 16 rows, shifted by its first row
   f32x8 x0 = colp, ssq = colp;
-  if constexpr (EPI == 9) x0 = to_f32(*reinterpret_cast<const bf16x8*>(lds + r0 * 512 + ((c ^ (r0 & 31)) << 4)));
+  if constexpr (epi_stats(EPI)) x0 = to_f32(*reinterpret_cast<const bf16x8*>(lds + r0 * 512 + ((c ^ (r0 & 31)) << 4)));
 #pragma unroll 4
   for (int it = 0; it < 16; ++it) {
     const int r = 16 * it + r0;
     const bf16x8 v = *reinterpret_cast<const bf16x8*>(lds + r * 512 + ((c ^ (r & 31)) << 4));
     const size_t m = (size_t)(m0 + r);
-    if constexpr (EPI <= 1) {
+    if constexpr (epi_plain_store(EPI)) {
       *reinterpret_cast<bf16x8*>(C + m * ldc + n) = v;
-    } else if constexpr (EPI == 9) {
+    } else if constexpr (EPI == EPI_STATS) {
       *reinterpret_cast<bf16x8*>(C + m * ldc + n) = v;
       const f32x8 d = to_f32(v) - x0;
       colp += d;
       ssq += d * d;
-    } else if constexpr (EPI == 2) {
+    } else if constexpr (EPI == EPI_GELU) {
       *reinterpret_cast<bf16x8*>(C + m * ldc + n) = v;
       const f32x8 x = to_f32(v) + bv8;
       f32x8 y;
 #pragma unroll
       for (int e = 0; e < 8; ++e) y[e] = gelu_sig(x[e]);
       *reinterpret_cast<bf16x8*>(Y + m * ldy + n) = to_bf16(y);
-    } else if constexpr (EPI == 4 || EPI == 5) {
+    } else if constexpr (EPI == EPI_ADD || EPI == EPI_BIAS_ADD) {
       // the addend joins after the bf16 staging: two roundings (the 4-wave path has one)
       const f32x8 r = to_f32(*reinterpret_cast<const bf16x8*>(Y + m * ldy + n));
       *reinterpret_cast<bf16x8*>(C + m * ldc + n) = to_bf16(to_f32(v) + r);
-    } else if constexpr (EPI == 6) {
+    } else if constexpr (EPI == EPI_ADD_MASKED) {
       // the addend masked by its keep bits (8 columns per byte): a branch gradient's ReLU
       f32x8 r = to_f32(*reinterpret_cast<const bf16x8*>(Y + m * ldy + n));
       const unsigned bits = reinterpret_cast<const unsigned char*>(bias)[(m * ldy + n) >> 3];
 #pragma unroll
       for (int q = 0; q < 8; ++q) r[q] = (bits >> q) & 1u ? r[q] : 0.f;
       *reinterpret_cast<bf16x8*>(C + m * ldc + n) = to_bf16(to_f32(v) + r);
-    } else {
+    } else if constexpr (EPI == EPI_DGELU) {
       const f32x8 x = to_f32(*reinterpret_cast<const bf16x8*>(Y + m * ldy + n)) + bv8;
       const f32x8 dy = to_f32(v);
       f32x8 d;
@@ -239,10 +245,10 @@ __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(const bf16* __restrict__ 
       *reinterpret_cast<bf16x8*>(C + m * ldc + n) = to_bf16(d);
     }
   }
-  if constexpr (EPI == 9) {
+  if constexpr (epi_stats(EPI)) {
     // 16 rows per thread → lanes l, l + 32 (rows r0 = 2w, 2w + 1) → the 8 waves
     // through LDS (the staged tile is dead after this barrier): one 256-row
-    // group per M-tile, partial row tm of [M/256][2][N]
+    // group per M-tile, partial row STATS_PER_TILE · tm of [M/256][2][N]
     f32x8 sum = colp + 16.f * x0, m2 = ssq - colp * colp * (1.f / 16.f), s2, q2;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -266,16 +272,16 @@ __global__ __launch_bounds__(NTHR) void gemm_nt_kernel(const bf16* __restrict__ 
         q += qb + d * d * (32.f * k * 32.f / (32.f * (k + 1)));
         s += sb;
       }
-      dbias_part[(size_t)tm * 2 * N + n0 + tid] = s;
-      dbias_part[(size_t)tm * 2 * N + N + n0 + tid] = q;
+      dbias_part[(size_t)(STATS_PER_TILE * tm) * 2 * N + n0 + tid] = s;
+      dbias_part[(size_t)(STATS_PER_TILE * tm) * 2 * N + N + n0 + tid] = q;
     }
   }
-  if constexpr (EPI == 3) {
+  if constexpr (epi_col_partials(EPI)) {
     // lanes l and l+32 share a column chunk: one fp32 partial row per wave
 #pragma unroll
     for (int e = 0; e < 8; ++e) colp[e] += __shfl_xor(colp[e], 32, 64);
     if (lane < 32) {
-      float* prow = dbias_part + (size_t)(8 * tm + w) * N + n;
+      float* prow = dbias_part + (size_t)(DBIAS_PER_TILE * tm + w) * N + n;
       *reinterpret_cast<f32x4*>(prow) = f32x4{colp[0], colp[1], colp[2], colp[3]};
       *reinterpret_cast<f32x4*>(prow + 4) = f32x4{colp[4], colp[5], colp[6], colp[7]};
     }
@@ -301,12 +307,11 @@ int gemm_nt_ok(int M, int N, int K, int lda, int ldb, int ldc) {
          ldc % 4 == 0 && lda >= K && ldb >= K && ldc >= N;
 }
 
-// partial rows of the EPI 3 / 8 bias gradient: 8 per 256-row tile on the 8-wave
-// ring, 2 on the 4-wave mainloop (its lane groups merge in-register)
-int gemm_nt_dbias_rows(int M, int K) { return (nt4_path(K) ? 2 : 8) * (M / BM); }
+// partial rows of the bias gradient (epi_col_partials) and rows per BatchNorm partial (EPI_STATS): each
+// mainloop's own layout, defined beside its kernel
+int gemm_nt_dbias_rows(int M, int K) { return nt4_path(K) ? gemm_nt4_dbias_rows(M) : DBIAS_PER_TILE * (M / BM); }
 int gemm_nt_epi_ok(int M, int N, int K) { return gemm_nt_ok(M, N, K, K, K, N) && nt4_path(K); }
-// rows per BatchNorm partial of EPI 9: a (tile, wm) half on the 4-wave mainloop, the tile on the ring
-int gemm_nt_stats_rows(int K) { return nt4_path(K) ? BM / 2 : BM; }
+int gemm_nt_stats_rows(int K) { return nt4_path(K) ? gemm_nt4_stats_rows() : BM / STATS_PER_TILE; }
 void gemm_nt_set_impl(int impl) { g_impl = impl; }
 
 int gemm_nt_get_impl() { return g_impl; }
@@ -314,28 +319,17 @@ int gemm_nt_get_impl() { return g_impl; }
 int gemm_nt(const bf16* A, const bf16* B, int M, int N, int K, int lda, int ldb, bf16* C, int ldc, int epi,
             const bf16* bias, bf16* Y, int ldy, float* dbias_part, hipStream_t st) {
   if (!gemm_nt_ok(M, N, K, lda, ldb, ldc)) return -2;
-  if (((epi >= 1 && epi <= 3) || (epi >= 5 && epi <= 7)) && !bias) return -3;  // EPI 6: bias = the addend's keep mask
-  if (epi == 6 && ldy % 8) return -3;
-  if (epi >= 2 && epi != 9 && (!Y || ldy % 4 || ldy < N)) return -3;
-  if ((epi == 3 || epi == 8 || epi == 9) && !dbias_part) return -3;
-  if ((epi == 7 || epi == 8) && !nt4_path(K)) return -4;  // the saved-GELU' pair: 4-wave mainloop only
+  if (const int rc = gemm_nt_args_rc(epi, bias, Y, ldy, N, dbias_part, nt4_path(K))) return rc;
   if (nt4_path(K))
     return gemm_nt4(A, B, M, N, K, lda, ldb, C, ldc, epi, bias, Y, ldy, dbias_part, st);
   const long long grid = (long long)(M / BM) * (N / BN);
   if (grid > 0x7fffffffLL) return -2;
   const int nk = K / BK;
-  switch (epi) {
-    case 0: gemm_nt_kernel<0><<<(int)grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, nk, C, ldc, bias, Y, ldy, dbias_part); break;
-    case 1: gemm_nt_kernel<1><<<(int)grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, nk, C, ldc, bias, Y, ldy, dbias_part); break;
-    case 2: gemm_nt_kernel<2><<<(int)grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, nk, C, ldc, bias, Y, ldy, dbias_part); break;
-    case 3: gemm_nt_kernel<3><<<(int)grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, nk, C, ldc, bias, Y, ldy, dbias_part); break;
-    case 4: gemm_nt_kernel<4><<<(int)grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, nk, C, ldc, bias, Y, ldy, dbias_part); break;
-    case 5: gemm_nt_kernel<5><<<(int)grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, nk, C, ldc, bias, Y, ldy, dbias_part); break;
-    case 6: gemm_nt_kernel<6><<<(int)grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, nk, C, ldc, bias, Y, ldy, dbias_part); break;
-    case 9: gemm_nt_kernel<9><<<(int)grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, nk, C, ldc, bias, Y, ldy, dbias_part); break;
-    default: return -4;
-  }
-  return 0;
+  using Ring = std::integer_sequence<int, EPI_PLAIN, EPI_BIAS, EPI_GELU, EPI_DGELU, EPI_ADD, EPI_BIAS_ADD, EPI_ADD_MASKED, EPI_STATS>;
+  return nt_epi_dispatch(Ring{}, epi, [&](auto e) {
+    gemm_nt_kernel<decltype(e)::value><<<(int)grid, NTHR, 0, st>>>(A, B, lda, ldb, M, N, nk, C, ldc, bias, Y, ldy, dbias_part);
+    return 0;
+  });
 }
 
 }  // namespace pdo

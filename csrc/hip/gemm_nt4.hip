@@ -51,6 +51,7 @@
 #include <utility>
 
 #include "cdna4.h"
+#include "gemm_nt_epi.h"
 #include "kernels.h"
 
 namespace pdo {
@@ -59,6 +60,9 @@ namespace {
 
 constexpr int BM = 256, BN = 256, BK = 64, NTHR = 256;
 constexpr int OPB = 256 * BK * 2;  // bytes of one operand tile [256][64] bf16 = 32 KiB
+// partial rows per 256-row tile, bias gradient (epi_col_partials) and EPI_STATS alike: one per wm half, row
+// PART_PER_TILE · tm + wm (the kernel's index expressions and gemm_nt4_dbias_rows / gemm_nt4_stats_rows read this)
+constexpr int PART_PER_TILE = 2;
 
 // MIR: runs of 8 MFMAs share the SrcA operand (A fragment i, as hipBLASLt's
 //      loop does) and the operands trade places in the read / release / refill
@@ -70,6 +74,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
                                                            const bf16* __restrict__ bias, bf16* __restrict__ Y,
                                                            int ldy, float* __restrict__ dbias_part, int group_m,
                                                            unsigned* __restrict__ sched) {
+  static_assert(epi_known(EPI), "no such epilogue");
   __shared__ __attribute__((aligned(16))) bf16 smem[2 * 2 * 256 * BK];  // [buf][A|B][256][64]
   __shared__ int s_next;  // dynamic order: the next virtual tile id, wave 0 → all
   const int tid = threadIdx.x, lane = tid & 63;
@@ -182,9 +187,9 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
   bf16x8 fa0[8], fb0[8], fa1[8], fb1[8];
   // the last k-tile of a tile issues the NEXT tile's first two k-tiles (after its
   // own last LDS reads, s ≥ 49) instead of the tile boundary doing it: ≈ 80 MFMAs
-  // more lead for those pieces.  EPI 8 also loads the first 16 of the epilogue's
+  // more lead for those pieces.  EPI_DGELU_SAVED also loads the first 16 of the epilogue's
   // 32 gelu' rows there (into fa0 / fb0's registers, dead after slot 63)
-  constexpr bool EARLY8 = EPI == 8;
+  constexpr bool EARLY8 = EPI == EPI_DGELU_SAVED;
   bool has_next = false;
   int ntm = 0, ntn = 0;
   Src nx0{}, nx1{};
@@ -216,10 +221,10 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
     const int g4 = lane >> 4;
     const int nb = n0 + wn * 128 + 8 * (lane & 15);
     const size_t mr = (size_t)(m0 + wm * 128 + 4 * g4);
-    // EPI 3: the GELU pre-activation; EPI 4 / 5 / 6: the addend; EPI 8: the saved GELU'
-    constexpr bool PRE = EPI >= 3 && EPI != 7 && EPI != 9;
+    // what Y holds: EPI_DGELU the GELU pre-activation, the three EPI_*ADD* the addend, EPI_DGELU_SAVED the saved GELU'
+    constexpr bool PRE = epi_reads_y(EPI);
     bf16x8 pre[PRE ? 32 : 1];
-    unsigned char mk[EPI == 6 ? 32 : 1];  // EPI 6: the addend's keep bits (8 columns per byte)
+    unsigned char mk[EPI == EPI_ADD_MASKED ? 32 : 1];  // the addend's keep bits (8 columns per byte)
     if constexpr (PRE) {
 #pragma unroll
       for (int u = 0; u < 32; ++u) {
@@ -232,17 +237,17 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
         pre[u] = *reinterpret_cast<const bf16x8*>(Y + (mr + 16 * (u >> 2) + (u & 3)) * ldy + nb);
       }
     }
-    if constexpr (EPI == 6) {
+    if constexpr (EPI == EPI_ADD_MASKED) {
       const unsigned char* mask = reinterpret_cast<const unsigned char*>(bias);
 #pragma unroll
       for (int u = 0; u < 32; ++u) mk[u] = mask[((mr + 16 * (u >> 2) + (u & 3)) * ldy + nb) >> 3];
     }
     f32x8 bv8 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if constexpr ((EPI >= 1 && EPI <= 3) || EPI == 5 || EPI == 7) bv8 = to_f32(*reinterpret_cast<const bf16x8*>(bias + nb));
+    if constexpr (epi_bias_into_c(EPI) || epi_bias_into_activation(EPI)) bv8 = to_f32(*reinterpret_cast<const bf16x8*>(bias + nb));
     f32x8 colp = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     f32x2 m1 = {-1.f, -1.f};
     asm volatile("" : "+v"(m1));
-    // EPI 9: BatchNorm statistics of the bf16 outputs — per lane its 8 columns
+    // EPI_STATS: BatchNorm statistics of the bf16 outputs — per lane its 8 columns
     // over the 32 rows it holds (16i + 4(l >> 4) + e), shifted by the first row
     // (x0) so Σd² − (Σd)²/32 does not cancel when |mean| ≫ std
     f32x8 x0 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ssum = x0, ssq = x0;
@@ -256,9 +261,9 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
         const f32x8 v = {a[0][e], a[1][e], a[2][e], a[3][e], a[4][e], a[5][e], a[6][e], a[7][e]};
         const size_t m = mr + 16 * i + e;
         bf16* crow = C + m * ldc + nb;
-        if constexpr (EPI <= 1) {
+        if constexpr (epi_plain_store(EPI)) {
           st16(crow, to_bf16(v + bv8));
-        } else if constexpr (EPI == 9) {
+        } else if constexpr (EPI == EPI_STATS) {
           const bf16x8 o = to_bf16(v);
           st16(crow, o);
           const f32x8 r = to_f32(o);
@@ -266,7 +271,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
           const f32x8 d = r - x0;
           ssum += d;
           ssq += d * d;
-        } else if constexpr (EPI == 2) {
+        } else if constexpr (EPI == EPI_GELU) {
           // GELU of the fp32 pre-activation (the bf16 copy is stored for the
           // backward, as hipBLASLt's GELU_AUX epilogue does); no bf16 round trip:
           // the fused epilogues' cost is their VALU count with the matrix pipe
@@ -281,7 +286,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
             y[q + 1] = gg[1];
           }
           st16(Y + m * ldy + nb, to_bf16(y));
-        } else if constexpr (EPI == 7) {
+        } else if constexpr (EPI == EPI_GELU_SAVE_GRAD) {
           // fc1 with the derivative saved instead of the pre-activation: C =
           // gelu'(x), Y = gelu(x), x = the fp32 product + bias
           const f32x8 x = v + bv8;
@@ -297,23 +302,23 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
           }
           st16(crow, to_bf16(g));
           st16(Y + m * ldy + nb, to_bf16(y));
-        } else if constexpr (EPI == 8) {
+        } else if constexpr (EPI == EPI_DGELU_SAVED) {
           // fc2's input gradient against the saved GELU': C = (A·Bᵀ) ⊙ Y, + bias-gradient partials
           const f32x8 d = v * to_f32(pre[4 * i + e]);
           colp += d;
           st16(crow, to_bf16(d));
-        } else if constexpr (EPI == 4) {
+        } else if constexpr (EPI == EPI_ADD) {
           st16(crow, to_bf16(v + to_f32(pre[4 * i + e])));  // C = A·Bᵀ + Y, one rounding
-        } else if constexpr (EPI == 5) {
+        } else if constexpr (EPI == EPI_BIAS_ADD) {
           st16(crow, to_bf16(v + bv8 + to_f32(pre[4 * i + e])));  // C = A·Bᵀ + bias + Y (residual stream)
-        } else if constexpr (EPI == 6) {
+        } else if constexpr (EPI == EPI_ADD_MASKED) {
           // C = A·Bᵀ + Y ⊙ keep: a branch gradient whose ReLU mask is applied here
           const unsigned bits = mk[4 * i + e];
           f32x8 r = to_f32(pre[4 * i + e]);
 #pragma unroll
           for (int q = 0; q < 8; ++q) r[q] = (bits >> q) & 1u ? r[q] : 0.f;
           st16(crow, to_bf16(v + r));
-        } else {
+        } else if constexpr (EPI == EPI_DGELU) {
           const f32x8 x = to_f32(pre[4 * i + e]) + bv8;
           const f32x8& dy = v;  // the fp32 product, not its bf16 rounding
           f32x8 d;
@@ -328,10 +333,10 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
         }
       }
     }
-    if constexpr (EPI == 9) {
+    if constexpr (epi_stats(EPI)) {
       // this lane's 32 rows, then the four lane groups (same columns, rows
       // 4·g4 + …) merged by xor-16 / xor-32 exchanges: one 128-row group per
-      // (M-tile, wm), partial row 2·tm + wm of [M/128][2][N]
+      // (M-tile, wm), partial row PART_PER_TILE·tm + wm of [M/128][2][N]
       f32x8 sum = ssum + 32.f * x0, m2 = ssq - ssum * ssum * (1.f / 32.f);
       float n = 32.f;
 #pragma unroll
@@ -346,23 +351,23 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt4_kernel(const bf16* __restric
         n *= 2.f;
       }
       if (g4 == 0) {
-        float* prow = dbias_part + (size_t)(2 * tm + wm) * 2 * N + nb;
+        float* prow = dbias_part + (size_t)(PART_PER_TILE * tm + wm) * 2 * N + nb;
         *reinterpret_cast<f32x4*>(prow) = f32x4{sum[0], sum[1], sum[2], sum[3]};
         *reinterpret_cast<f32x4*>(prow + 4) = f32x4{sum[4], sum[5], sum[6], sum[7]};
         *reinterpret_cast<f32x4*>(prow + N) = f32x4{m2[0], m2[1], m2[2], m2[3]};
         *reinterpret_cast<f32x4*>(prow + N + 4) = f32x4{m2[4], m2[5], m2[6], m2[7]};
       }
     }
-    if constexpr (EPI == 3 || EPI == 8) {
+    if constexpr (epi_col_partials(EPI)) {
       // the four lane groups (same 8 columns, rows 4·g4 + …) merged by xor-16 /
-      // xor-32 exchanges: partial row 2·tm + wm (gemm_nt4_dbias_rows) holds this
+      // xor-32 exchanges: partial row PART_PER_TILE·tm + wm (gemm_nt4_dbias_rows) holds this
       // wave's 128 rows — a quarter of the partial bytes of one row per lane group
 #pragma unroll
       for (int x = 16; x <= 32; x *= 2)
 #pragma unroll
         for (int k = 0; k < 8; ++k) colp[k] += __shfl_xor(colp[k], x, 64);
       if (g4 == 0) {
-        float* prow = dbias_part + (size_t)(2 * tm + wm) * N + nb;
+        float* prow = dbias_part + (size_t)(PART_PER_TILE * tm + wm) * N + nb;
         *reinterpret_cast<f32x4*>(prow) = f32x4{colp[0], colp[1], colp[2], colp[3]};
         *reinterpret_cast<f32x4*>(prow + 4) = f32x4{colp[4], colp[5], colp[6], colp[7]};
       }
@@ -603,6 +608,9 @@ static int persistent_grid(long long tiles) {
   return (int)(tiles < ncu ? tiles : ncu);
 }
 
+int gemm_nt4_dbias_rows(int M) { return PART_PER_TILE * (M / BM); }
+int gemm_nt4_stats_rows() { return BM / PART_PER_TILE; }
+
 // B-stationary runs for K ≤ 1024, mirrored above (tools/nt4_probe.py,
 // profiles/r3_gemm_nt4_rows.md)
 int gemm_nt4(const bf16* A, const bf16* B, int M, int N, int K, int lda, int ldb, bf16* C, int ldc, int epi,
@@ -623,20 +631,9 @@ int gemm_nt4(const bf16* A, const bf16* B, int M, int N, int K, int lda, int ldb
     return 0;
   };
   auto launch = [&](auto mir_tag) -> int {
-    constexpr bool MI = decltype(mir_tag)::value;
-    switch (epi) {
-      case 0: return go(gemm_nt4_kernel<0, MI>);
-      case 1: return go(gemm_nt4_kernel<1, MI>);
-      case 2: return go(gemm_nt4_kernel<2, MI>);
-      case 3: return go(gemm_nt4_kernel<3, MI>);
-      case 4: return go(gemm_nt4_kernel<4, MI>);
-      case 5: return go(gemm_nt4_kernel<5, MI>);
-      case 6: return go(gemm_nt4_kernel<6, MI>);
-      case 7: return go(gemm_nt4_kernel<7, MI>);
-      case 8: return go(gemm_nt4_kernel<8, MI>);
-      case 9: return go(gemm_nt4_kernel<9, MI>);
-      default: return -4;
-    }
+    return nt_epi_dispatch(std::make_integer_sequence<int, EPI_COUNT>{}, epi, [&](auto e) {
+      return go(gemm_nt4_kernel<decltype(e)::value, decltype(mir_tag)::value>);
+    });
   };
   return K > 1024 ? launch(std::true_type{}) : launch(std::false_type{});
 }

@@ -190,14 +190,11 @@ int gemm_dw4_grouped(const DwProblem* probs, int n, hipStream_t st);
 // which mainloop gemm_dw() runs: 0 = 8-wave (gemm_dw.hip), 1.. = 4-wave variant impl - 1
 void gemm_dw_set_impl(int impl);
 int gemm_dw_get_impl();
-// transpose.hip: out[C][R] = in[R][C], R and C multiples of 64
-// gemm_nt.hip: C[M][N] = A[M][K]·B[N][K]ᵀ with a fused epilogue
-// (0 plain, 1 +bias, 2 C = pre-activation & Y = gelu(C + bias),
-//  3 C = (A·Bᵀ)⊙gelu'(Y + bias) & fp32 column partials [gemm_nt_dbias_rows(M, K)][N])
+// gemm_nt.hip: C[M][N] = A[M][K]·B[N][K]ᵀ with the fused epilogue `epi`, an NtEpi of gemm_nt_epi.h (names, contract)
 int gemm_nt_ok(int M, int N, int K, int lda, int ldb, int ldc);
-// EPI 7 / 8 / 9 (the 4-wave mainloop's epilogues) apply to this product
+// the 4-wave mainloop runs this product, so its own epilogues (epi_nt4_only) and EPI_STATS at N % 256 = 128 apply
 int gemm_nt_epi_ok(int M, int N, int K);
-// rows per BatchNorm partial row of EPI 9 (gemm_nt with the statistics epilogue)
+// rows per BatchNorm partial row of EPI_STATS; fp32 partial rows [gemm_nt_dbias_rows(M, K)][N] of EPI_DGELU / EPI_DGELU_SAVED
 int gemm_nt_stats_rows(int K);
 int gemm_nt_dbias_rows(int M, int K);
 int gemm_nt(const bf16* A, const bf16* B, int M, int N, int K, int lda, int ldb, bf16* C, int ldc, int epi,
@@ -205,13 +202,16 @@ int gemm_nt(const bf16* A, const bf16* B, int M, int N, int K, int lda, int ldb,
 // gemm_nt4.hip: the same contract on the 4-wave / 128 × 128-per-wave mainloop
 int gemm_nt4(const bf16* A, const bf16* B, int M, int N, int K, int lda, int ldb, bf16* C, int ldc, int epi,
              const bf16* bias, bf16* Y, int ldy, float* dbias_part, hipStream_t st);
-// (N % 256 = 128 allowed: half-width last tile column)
+// (N % 256 = 128 allowed: half-width last tile column); its partial-row layout, for the two queries above
+int gemm_nt4_dbias_rows(int M);
+int gemm_nt4_stats_rows();
 // which mainloop gemm_nt() runs: 0 = 8-wave ring (gemm_nt.hip), 1 = 4-wave
 // (gemm_nt4.hip, default)
 void gemm_nt_set_impl(int impl);
 // gemm_nt4 tile order: 1 = dynamic per-XCD counters, 0 = static (default; experiments only)
 void gemm_nt4_set_dynamic(int on);
 int gemm_nt_get_impl();
+// transpose.hip: out[C][R] = in[R][C], R and C multiples of 64
 int transpose_bf16(const bf16* in, bf16* out, int R, int C, hipStream_t st);
 // every matrix of a table in one launch: table = n × {first tile, src offset, dst
 // offset, R, C} int64 (device), elements relative to src / dst; tiles = Σ (R/64)(C/64)
