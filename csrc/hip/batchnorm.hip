@@ -14,6 +14,8 @@
 //   backward: stats    — Σg, Σg·(x−mean), g = dy·[pre-activation > 0]
 //             finalize — dgamma, dbeta and the dx coefficients
 //             apply    — dx = k·g − k·Σg/M − k·invstd·Σg·x̂/M  [+ dresidual = g]
+//   inference: bn_eval_ss — scale/shift from the running statistics — then the
+//             same apply kernels (no ReLU mask, no statistics, nothing saved)
 // Without a residual the ReLU mask is recomputed from x (bit-identical
 // x·scale + shift through the same helper), so y is neither saved nor re-read.
 // Per-block fp32 atomics into one [2C] buffer were tried instead of partials +
@@ -540,6 +542,9 @@ __global__ __launch_bounds__(256) void bn_finalize_tiles_kernel(const float* __r
 // fixed along its loop).
 typedef uint8_t u8x8 __attribute__((ext_vector_type(8)));
 
+// SAVE = false (inference, bn_relu_pool_eval): only the pooled activation is written;
+// arg and xsel are not touched (null)
+template <bool SAVE>
 __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const bf16* __restrict__ x, const float* __restrict__ ss,
                                                                int N, int H, int W, int C, int OH, int OW,
                                                                bf16* __restrict__ y, uint8_t* __restrict__ arg,
@@ -586,8 +591,10 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const bf16* __res
       }
     }
     reinterpret_cast<bf16x8*>(y)[j] = to_bf16(best);  // j = ((n·OH + oh)·OW + ow)·C8 + c8
-    reinterpret_cast<u8x8*>(arg)[j] = pos;
-    reinterpret_cast<bf16x8*>(xsel)[j] = to_bf16(xb);  // exact: xb is a bf16 input value
+    if (SAVE) {
+      reinterpret_cast<u8x8*>(arg)[j] = pos;
+      reinterpret_cast<bf16x8*>(xsel)[j] = to_bf16(xb);  // exact: xb is a bf16 input value
+    }
   }
 }
 
@@ -912,8 +919,45 @@ int bn_relu_pool_fwd_tiles(const float* tile_part, int G, int tile_rows, const b
                  st);
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   const int tot = N * OH * OW * (C / 8);
-  bn_relu_pool_fwd_kernel<<<(unsigned)min((tot + 255) / 256, 8192), 256, 0, st>>>(x, ss, N, H, W, C, OH, OW, y, arg,
-                                                                                 xsel);
+  bn_relu_pool_fwd_kernel<true><<<(unsigned)min((tot + 255) / 256, 8192), 256, 0, st>>>(x, ss, N, H, W, C, OH, OW, y,
+                                                                                       arg, xsel);
+  return 0;
+}
+
+// ---- inference: scale / shift from the running statistics, then the apply kernels ----
+__global__ __launch_bounds__(256) void bn_eval_ss_kernel(const float* __restrict__ rm, const float* __restrict__ rv,
+                                                         const float* __restrict__ w, const float* __restrict__ b,
+                                                         int C, float eps, float* __restrict__ ss) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const float sc = w[c] * rsqrtf(rv[c] + eps);
+  ss[c] = sc;
+  ss[C + c] = b[c] - rm[c] * sc;
+}
+
+int bn_eval_ss(const float* running_mean, const float* running_var, const float* w, const float* b, int C, float eps,
+               float* ss, hipStream_t st) {
+  if (C < 1) return -2;
+  bn_eval_ss_kernel<<<(C + 255) / 256, 256, 0, st>>>(running_mean, running_var, w, b, C, eps, ss);
+  return 0;
+}
+
+int bn_apply_eval(const bf16* x, const bf16* res, const float* ss, const float* rss, long long M, int C, int relu,
+                  bf16* y, hipStream_t st) {
+  if (C % 8 != 0 || M < 1 || M * C / 8 >= (1ll << 32) || (rss != nullptr && res == nullptr)) return -2;
+  const long long n8 = M * C / 8;
+  const unsigned g = apply_grid(n8);
+  if (256 % (C / 8) == 0) bn_apply_kernel<true><<<g, 256, 0, st>>>(x, res, ss, n8, C, relu, y, nullptr, rss);
+  else bn_apply_kernel<false><<<g, 256, 0, st>>>(x, res, ss, n8, C, relu, y, nullptr, rss);
+  return 0;
+}
+
+int bn_relu_pool_eval(const bf16* x, const float* ss, int N, int H, int W, int C, bf16* y, hipStream_t st) {
+  if (!pool_bn_ok(N, H, W, C)) return -2;
+  const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
+  const int tot = N * OH * OW * (C / 8);
+  bn_relu_pool_fwd_kernel<false><<<(unsigned)min((tot + 255) / 256, 8192), 256, 0, st>>>(x, ss, N, H, W, C, OH, OW, y,
+                                                                                        nullptr, nullptr);
   return 0;
 }
 

@@ -394,14 +394,21 @@ void adamw_flat(at::Tensor p, at::Tensor g, at::Tensor master, at::Tensor m1, at
                            cur_stream()), "adamw_flat");
 }
 
+// lr_dev (optional, float32 [1] on w's device): the rate is read from it instead of lr
 void sgd_flat(at::Tensor w, at::Tensor g, at::Tensor buf, at::Tensor decay, double lr, double mom, double wd,
-              double grad_scale) {
+              double grad_scale, std::optional<at::Tensor> lr_dev) {
   CHECK_IN(w); CHECK_IN(g); CHECK_IN(buf); CHECK_IN(decay);
   CHECK_F32(w); CHECK_F32(g); CHECK_F32(buf); CHECK_F32(decay);
   const long long n = w.numel();
   TORCH_CHECK(g.numel() == n && buf.numel() == n && n % 1024 == 0 && decay.numel() == n / 1024);
+  const float* lp = nullptr;
+  if (lr_dev) {
+    CHECK_IN(*lr_dev); CHECK_F32(*lr_dev);
+    TORCH_CHECK(lr_dev->numel() == 1 && lr_dev->device() == w.device(), "sgd_flat: lr_dev is one float on w's device");
+    lp = fp(*lr_dev);
+  }
   CHECK_RC(pdo::sgd_flat(fp(w), fp(g), fp(buf), fp(decay), n, (float)lr, (float)mom, (float)wd, (float)grad_scale,
-                         cur_stream()), "sgd_flat");
+                         cur_stream(), lp), "sgd_flat");
 }
 
 // out (+)= sum over the leading dim of part [s, ...] (split-K weight gradients)
@@ -1089,6 +1096,71 @@ std::vector<at::Tensor> bn_relu_pool_fwd_tiles(at::Tensor x, at::Tensor stats, i
   return {y, arg, xsel, mean, invstd};
 }
 
+// ---------------------------------------------------------------- inference BatchNorm (running statistics)
+// ss = (scale | shift) [2, C] of one BatchNorm's running statistics (bn_eval_ss); reads only
+static at::Tensor bn_eval_ss_of(const at::Tensor& w, const at::Tensor& b, const at::Tensor& rm, const at::Tensor& rv,
+                                double eps, int64_t C) {
+  CHECK_IN(w); CHECK_IN(b); CHECK_IN(rm); CHECK_IN(rv);
+  CHECK_F32(w); CHECK_F32(b); CHECK_F32(rm); CHECK_F32(rv);
+  TORCH_CHECK(w.numel() == C && b.numel() == C && rm.numel() == C && rv.numel() == C,
+              "bn_act_eval: weight, bias and running statistics must hold C values");
+  auto ss = at::empty({2 * C}, w.options());
+  CHECK_RC(pdo::bn_eval_ss(fp(rm), fp(rv), fp(w), fp(b), (int)C, (float)eps, fp(ss), cur_stream()), "bn_eval_ss");
+  return ss;
+}
+
+// y = act(BN(x) [+ res]) from the running statistics: channels_last bf16 x (and res)
+at::Tensor bn_act_eval(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor w, at::Tensor b, at::Tensor rm,
+                       at::Tensor rv, double eps, bool relu) {
+  CHECK_BF16(x);
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "bn_act_eval: channels_last bf16 input");
+  const int64_t C = x.size(1), M = x.numel() / C;
+  TORCH_CHECK(C % 8 == 0, "bn_act_eval: C % 8 == 0");
+  const bf16* rp = nullptr;
+  if (res && res->defined()) {
+    TORCH_CHECK(res->sizes() == x.sizes() && res->is_contiguous(at::MemoryFormat::ChannelsLast) && res->is_cuda());
+    CHECK_BF16((*res));
+    rp = bp(*res);
+  }
+  auto ss = bn_eval_ss_of(w, b, rm, rv, eps, C);
+  auto y = at::empty_like(x, x.options(), at::MemoryFormat::ChannelsLast);
+  CHECK_RC(pdo::bn_apply_eval(bp(x), rp, fp(ss), nullptr, M, (int)C, relu ? 1 : 0, bp(y), cur_stream()),
+           "bn_apply_eval");
+  return y;
+}
+
+// y = act(BN(x) + BN_r(r)), both from their running statistics, one apply pass
+at::Tensor bn_act_eval_pair(at::Tensor x, at::Tensor w, at::Tensor b, at::Tensor rm, at::Tensor rv, double eps,
+                            at::Tensor r, at::Tensor rw, at::Tensor rb, at::Tensor rrm, at::Tensor rrv, double reps,
+                            bool relu) {
+  CHECK_BF16(x); CHECK_BF16(r);
+  TORCH_CHECK(x.is_cuda() && r.is_cuda() && x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+              r.sizes() == x.sizes() && r.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "bn_act_eval_pair: channels_last bf16 x and r of one shape");
+  const int64_t C = x.size(1), M = x.numel() / C;
+  TORCH_CHECK(C % 8 == 0, "bn_act_eval_pair: C % 8 == 0");
+  auto ss = bn_eval_ss_of(w, b, rm, rv, eps, C), rss = bn_eval_ss_of(rw, rb, rrm, rrv, reps, C);
+  auto y = at::empty_like(x, x.options(), at::MemoryFormat::ChannelsLast);
+  CHECK_RC(pdo::bn_apply_eval(bp(x), bp(r), fp(ss), fp(rss), M, (int)C, relu ? 1 : 0, bp(y), cur_stream()),
+           "bn_apply_eval");
+  return y;
+}
+
+// max_pool_3x3s2(ReLU(BN(x))) from the running statistics: only the pooled activation is written
+at::Tensor bn_relu_pool_eval(at::Tensor x, at::Tensor w, at::Tensor b, at::Tensor rm, at::Tensor rv, double eps) {
+  CHECK_BF16(x);
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "bn_relu_pool_eval: channels_last bf16 input");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(C % 8 == 0 && 256 % (C / 8) == 0, "bn_relu_pool_eval: C % 8 == 0 and (C / 8) | 256");
+  auto ss = bn_eval_ss_of(w, b, rm, rv, eps, C);
+  auto y = at::empty({N, C, (H - 1) / 2 + 1, (W - 1) / 2 + 1}, x.options(), at::MemoryFormat::ChannelsLast);
+  CHECK_RC(pdo::bn_relu_pool_eval(bp(x), fp(ss), (int)N, (int)H, (int)W, (int)C, bp(y), cur_stream()),
+           "bn_relu_pool_eval");
+  return y;
+}
+
 // its backward: [dx of the BatchNorm input, dgamma, dbeta] (dgamma / dbeta accumulated
 // into dw_into / db_into — the parameters' fp32 arena slices — when given)
 std::vector<at::Tensor> pool_bn_bwd(at::Tensor dy, at::Tensor y, at::Tensor xsel, at::Tensor arg, at::Tensor x,
@@ -1315,6 +1387,66 @@ py::object token_batch(std::optional<at::Tensor> tok, int64_t n, int64_t B, int6
   return py::make_tuple(idx, tgt);
 }
 
+// One micro-batch of image crops (image.hip): img = the stored uint8 set [n, R, R, 3] and lab
+// int32 [n], or with staged = true the [B, R, R, 3] / [B] buffers gathered on the host.
+// draw = (seed, stream, m, rank); norm = (sc[3], sh[3]).  Writes x (bf16 [B, res, res, 3]) and
+// y (int64 [B]) — the caller's when given — and returns (x, y).  boxes_out (int32 [B, 6])
+// receives the draw; img = None writes only the boxes (returns None).
+py::object image_batch(std::optional<at::Tensor> img, std::optional<at::Tensor> lab, int64_t n, int64_t B, int64_t R,
+                       int64_t res, std::tuple<std::array<double, 3>, std::array<double, 3>> norm,
+                       std::tuple<uint64_t, int64_t, uint64_t, int64_t> draw, int64_t Bglobal, bool staged,
+                       std::optional<at::Tensor> x_out, std::optional<at::Tensor> y_out,
+                       std::optional<at::Tensor> boxes_out) {
+  TORCH_CHECK(B >= 1 && B <= 65535, "image_batch: B in [1, 65535] required");
+  TORCH_CHECK(R >= 8 && R <= 4096 && res >= 8 && res <= R && res % 8 == 0,
+              "image_batch: 8 <= res <= R <= 4096 and res % 8 == 0 required, got R = ", R, ", res = ", res);
+  TORCH_CHECK(n >= 1 && n < (1LL << 31), "image_batch: 1 <= n < 2^31 images required");
+  const auto [seed, stream, m, rank] = draw;
+  TORCH_CHECK(stream == 0 || stream == 1, "image_batch: stream is 0 (training) or 1 (evaluation)");
+  TORCH_CHECK(rank >= 0 && (rank + 1) * B <= (1LL << 32), "image_batch: global row rank*B + j must stay below 2^32");
+  TORCH_CHECK(Bglobal >= B && Bglobal <= (1LL << 31), "image_batch: Bglobal = world*B, at most 2^31");
+  pdo::DataDraw d;
+  d.key0 = (uint32_t)seed;
+  d.key1 = (uint32_t)(seed >> 32);
+  d.stream = (uint32_t)stream;
+  d.step = (uint32_t)m;  // m mod 2^32
+  d.row0 = (uint64_t)rank * (uint64_t)B;
+  pdo::ImageNorm nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.sc[c] = (float)std::get<0>(norm)[c];
+    nm.sh[c] = (float)std::get<1>(norm)[c];
+  }
+  int* bxp = nullptr;
+  if (boxes_out) {
+    CHECK_IN(*boxes_out);
+    TORCH_CHECK(boxes_out->scalar_type() == at::kInt && boxes_out->numel() == B * 6,
+                "image_batch: boxes_out must be int32 [B, 6]");
+    bxp = boxes_out->data_ptr<int>();
+  }
+  if (!img) {
+    TORCH_CHECK(bxp != nullptr, "image_batch: img = None needs boxes_out");
+    CHECK_RC(pdo::image_batch(nullptr, nullptr, n, (int)B, (int)R, (int)res, nm, nullptr, nullptr, d, Bglobal, false,
+                              bxp, cur_stream()), "image_batch");
+    return py::none();
+  }
+  TORCH_CHECK(lab.has_value(), "image_batch: lab required with img");
+  CHECK_IN(*img); CHECK_IN(*lab);
+  TORCH_CHECK(img->scalar_type() == at::kByte && lab->scalar_type() == at::kInt,
+              "image_batch: img must be uint8 and lab int32");
+  const int64_t held = staged ? B : n;
+  TORCH_CHECK(img->numel() == held * R * R * 3 && lab->numel() == held && lab->device() == img->device(),
+              "image_batch: img must hold ", held, " images of ", R, " x ", R, " x 3 and lab as many labels");
+  TORCH_CHECK(!boxes_out || boxes_out->device() == img->device(), "image_batch: boxes_out on another device");
+  at::Tensor x = x_out ? *x_out : at::empty({B, res, res, 3}, img->options().dtype(at::kBFloat16));
+  at::Tensor y = y_out ? *y_out : at::empty({B}, img->options().dtype(at::kLong));
+  CHECK_IN(x); CHECK_IN(y); CHECK_BF16(x); CHECK_I64(y);
+  TORCH_CHECK(x.numel() == B * res * res * 3 && y.numel() == B && x.device() == img->device() &&
+              y.device() == img->device(), "image_batch: x must be bf16 [B, res, res, 3] and y int64 [B] on img's device");
+  CHECK_RC(pdo::image_batch(img->data_ptr<uint8_t>(), lab->data_ptr<int>(), n, (int)B, (int)R, (int)res, nm, bp(x),
+                            y.data_ptr<int64_t>(), d, Bglobal, staged, bxp, cur_stream()), "image_batch");
+  return py::make_tuple(x, y);
+}
+
 // flat[off_i : off_i + n_i] = scale * t_i for every tensor (one launch);
 // reverse: t_i = flat[off_i : off_i + n_i].  bf16 or f32, all one dtype.
 void flatten_scale(std::vector<at::Tensor> ts, at::Tensor flat, std::vector<int64_t> offsets, double scale,
@@ -1471,7 +1603,8 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.def("set_adamw_variant", [](int v) { pdo::adamw_set_variant(v); });
   m.def("sumsq_total", &sumsq_total);
   m.def("adamw_flat", &adamw_flat);
-  m.def("sgd_flat", &sgd_flat);
+  m.def("sgd_flat", &sgd_flat, py::arg("w"), py::arg("g"), py::arg("buf"), py::arg("decay"), py::arg("lr"),
+        py::arg("mom"), py::arg("wd"), py::arg("grad_scale"), py::arg("lr_dev") = py::none());
   m.def("splitk_add", &splitk_add);
   m.def("transpose", &transpose, py::arg("x"), py::arg("out") = py::none());
   m.def("transpose_batched", &transpose_batched);
@@ -1539,6 +1672,10 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.def("bn_act_bwd", &bn_act_bwd);
   m.def("maxpool3s2_fwd", &maxpool3s2_fwd);
   m.def("bn_relu_pool_fwd_tiles", &bn_relu_pool_fwd_tiles);
+  m.def("bn_act_eval", &bn_act_eval, py::arg("x"), py::arg("res"), py::arg("w"), py::arg("b"),
+        py::arg("running_mean"), py::arg("running_var"), py::arg("eps"), py::arg("relu"));
+  m.def("bn_act_eval_pair", &bn_act_eval_pair);
+  m.def("bn_relu_pool_eval", &bn_relu_pool_eval);
   m.def("pool_bn_bwd", &pool_bn_bwd, py::arg("dy"), py::arg("y"), py::arg("xsel"), py::arg("arg"), py::arg("x"),
         py::arg("mean"), py::arg("invstd"),
         py::arg("w"), py::arg("b"), py::arg("dw_into") = py::none(), py::arg("db_into") = py::none());
@@ -1555,6 +1692,9 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.def("grad_accum_fold", &grad_accum_fold, py::arg("g"), py::arg("acc"), py::arg("init"), py::arg("emit"));
   m.def("token_batch", &token_batch, py::arg("tok"), py::arg("n"), py::arg("B"), py::arg("S"), py::arg("vocab"),
         py::arg("bad") = py::none(), py::arg("draw") = py::none(), py::arg("starts_out") = py::none());
+  m.def("image_batch", &image_batch, py::arg("img"), py::arg("lab"), py::arg("n"), py::arg("B"), py::arg("R"),
+        py::arg("res"), py::arg("norm"), py::arg("draw"), py::arg("Bglobal"), py::arg("staged") = false,
+        py::arg("x_out") = py::none(), py::arg("y_out") = py::none(), py::arg("boxes_out") = py::none());
   m.def("flatten_scale", &flatten_scale);
   m.def("cast_scale_bf16_f32", &cast_scale_bf16_f32);
   m.def("cast_f32_bf16", &cast_f32_bf16);

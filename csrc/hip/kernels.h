@@ -143,6 +143,16 @@ int bn_relu_pool_fwd_tiles(const float* tile_part, int G, int tile_rows, const b
                            float* running_mean, float* running_var, int N, int H, int W, int C, float eps,
                            float momentum, bf16* y, uint8_t* arg, bf16* xsel, float* mean, float* invstd, float* ss,
                            hipStream_t st, float* merge = nullptr);
+// Inference BatchNorm (batchnorm.hip): bn_eval_ss turns running mean / var, γ, β, eps into
+// the ss = (scale | shift) rows [2][C] the apply kernels consume (scale = γ·rsqrt(var + eps),
+// shift = β − mean·scale); bn_apply_eval is y = act(x·scale + shift [+ res | + res·rscale +
+// rshift]) with no ReLU mask and no statistics written; bn_relu_pool_eval the stem's fused
+// BatchNorm + ReLU + 3×3/2 max-pool from ss, writing only the pooled activation.
+int bn_eval_ss(const float* running_mean, const float* running_var, const float* w, const float* b, int C, float eps,
+               float* ss, hipStream_t st);
+int bn_apply_eval(const bf16* x, const bf16* res, const float* ss, const float* rss, long long M, int C, int relu,
+                  bf16* y, hipStream_t st);
+int bn_relu_pool_eval(const bf16* x, const float* ss, int N, int H, int W, int C, bf16* y, hipStream_t st);
 int pool_bn_bwd_scratch_floats(int N, int H, int W, int C);
 int pool_bn_bwd(const bf16* dy, const bf16* y, const bf16* xsel, const uint8_t* arg, const bf16* x, const float* mean,
                 const float* invstd, const float* w, const float* b, int N, int H, int W, int C, bf16* dx, float* dw,
@@ -245,7 +255,9 @@ int embed_sorted_part_floats(int N, int C);
 int embed_bwd_sorted(const bf16* dy, const int64_t* keys, const int64_t* perm, bf16* dwte, bf16* dwpe, float* part,
                      int B, int S, int C, int Vp, int P, int accumulate, hipStream_t st);
 int sgd_flat(float* w, const float* g, float* buf, const float* decay_chunks, long long n, float lr, float mom,
-             float wd, float grad_scale, hipStream_t st);
+             float wd, float grad_scale, hipStream_t st, const float* lr_dev = nullptr);
+// lr_dev (optional): the rate is read from this device float instead of `lr` — a schedule
+// under a captured step, where a by-value argument is frozen at capture
 int cast_f32_bf16(const float* in, bf16* out, long long n, hipStream_t st);
 
 // optim.hip
@@ -299,5 +311,18 @@ struct DataDraw {
 // draw) receives the B starts; tok == nullptr writes only the starts.
 int token_batch(const uint16_t* tok, long long n, int B, int S, int vocab, int64_t* idx, int64_t* tgt,
                 unsigned long long* bad, const DataDraw* draw, int64_t* starts_out, hipStream_t st);
+
+// image.hip: one micro-batch of crops from a stored uint8 set [n][R][R][3] (labels int32 [n]) →
+// x bf16 [B][res][res][3] (NHWC) and y int64 [B]: draw of image index, crop box and flip
+// (DataDraw; stream 1 = the centred evaluation crop of image m·Bglobal + g, label −1 and a
+// zero image past n), bilinear resample, x = sum·sc[c] + sh[c].  staged: img / lab are
+// [B][R][R][3] / [B] buffers gathered on the host and row j reads entry j (the draw still
+// runs here).  R ≤ 4096, res % 8 == 0, 8 ≤ res ≤ R.  boxes_out (optional): int32 [B][6] =
+// i, x0, y0, cw, ch, flip; img == nullptr writes only the boxes.
+struct ImageNorm {
+  float sc[3], sh[3];
+};
+int image_batch(const uint8_t* img, const int* lab, long long n, int B, int R, int res, const ImageNorm& nm, bf16* x,
+                int64_t* y, const DataDraw& draw, long long Bglobal, bool staged, int* boxes_out, hipStream_t st);
 
 }  // namespace pdo

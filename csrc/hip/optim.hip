@@ -166,9 +166,35 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ w, const f
   }
 }
 
+// the same update with the rate read from device memory: a scheduled rate under a
+// captured step (a by-value lr is frozen at capture).  A kernel of its own, so
+// sgd_kernel's code object is the one it always was.
+__global__ __launch_bounds__(256) void sgd_lr_dev_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                         float* __restrict__ buf,
+                                                         const float* __restrict__ decay_chunks, long long n4,
+                                                         const float* __restrict__ lr_dev, float mom, float wd,
+                                                         float grad_scale) {
+  const float lr = *lr_dev;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const float dec = decay_chunks[i >> 8];
+    const f32x4 gi = reinterpret_cast<const f32x4*>(g)[i] * grad_scale;
+    f32x4 wi = reinterpret_cast<const f32x4*>(w)[i];
+    f32x4 b = reinterpret_cast<const f32x4*>(buf)[i];
+    b = mom * b + (gi + (wd * dec) * wi);
+    wi = wi - lr * b;
+    reinterpret_cast<f32x4*>(buf)[i] = b;
+    reinterpret_cast<f32x4*>(w)[i] = wi;
+  }
+}
+
 int sgd_flat(float* w, const float* g, float* buf, const float* decay_chunks, long long n, float lr, float mom,
-             float wd, float grad_scale, hipStream_t st) {
+             float wd, float grad_scale, hipStream_t st, const float* lr_dev) {
   if (n % 1024) return -2;
+  if (lr_dev != nullptr) {
+    sgd_lr_dev_kernel<<<stream_grid(n / 4, 256), 256, 0, st>>>(w, g, buf, decay_chunks, n / 4, lr_dev, mom, wd,
+                                                              grad_scale);
+    return 0;
+  }
   sgd_kernel<<<stream_grid(n / 4, 256), 256, 0, st>>>(w, g, buf, decay_chunks, n / 4, lr, mom, wd, grad_scale);
   return 0;
 }

@@ -30,6 +30,10 @@ its table, the cross-entropy skips the position) and is counted;
 :meth:`TokenStream.check` raises with the file name and the count.  On a GPU
 the count lives on the device and is read only where the trainer already
 synchronises.
+
+The ResNet trainer's image directories follow the same conventions:
+:class:`ImageStream`, :func:`crop_boxes`, :func:`image_batch_ref` and ``IMAGE_DOC``
+in the second half of this module (kernel ``csrc/hip/image.hip``).
 """
 from __future__ import annotations
 
@@ -188,6 +192,318 @@ class TokenStream:
 
     def close(self):
         if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+            self._next = None
+
+
+# ----------------------------------------------------------------------------------------------
+# Image files and the replayable crop sampler of the ResNet trainer
+# ----------------------------------------------------------------------------------------------
+IMAGE_DOC = """
+**File format.**  A directory with ``images.npy`` (uint8 ``[n, R, R, 3]``, RGB, square, C
+order, ``R ≤ 4096``) and ``labels.npy`` (any integer dtype, ``[n]``, each in
+``[0, classes)``), both opened with ``np.load(mmap_mode="r")``.  The model input is
+``res × res`` with ``res % 8 == 0`` and ``8 ≤ res ≤ R``.
+
+**Sampler.**  Counter-based like the token windows: the crops of micro-batch ``m`` are a pure
+function of ``(seed, stream, m)``; row ``j`` of rank ``rank`` is global row ``g = rank·B + j``
+(``g < 2³²``), key = (low, high) words of the 64-bit seed, and every value below is an unsigned
+64-bit integer.  Training (stream 0) is a random-resized crop (area in [0.08, 1), aspect in
+[3/4, 4/3]) and a flip:
+
+* call A, counter ``(g, 0, stream, m)``: ``i = ((w1 << 32) | w0) mod n``, ``flip = w2 & 1``;
+* call B, counter ``(g, 1, stream, m)`` → ``v0 … v3``:
+  ``f = 5243 + (((v0 >> 16)·60293) >> 16)`` (area fraction, Q16),
+  ``s = isqrt((f·R²) << 16)`` (side, Q16),
+  ``t = 65536 + (((v1 >> 16)·10138) >> 16)`` (√ratio, Q16, in [1, √(4/3))),
+  ``a = (s·t) >> 32``, ``b = ((s << 16) / t) >> 16``,
+  ``(cw, ch) = (a, b) if v1 & 1 else (b, a)``, each clamped to ``[1, R]``,
+  ``x0 = (v2·(R − cw + 1)) >> 32``, ``y0 = (v3·(R − ch + 1)) >> 32``.
+
+Evaluation (stream 1) is not random: ``i = m·Bglobal + g`` (``Bglobal = world·B``), the centred
+``res × res`` box (``x0 = y0 = (R − res) // 2``), no flip; a row with ``i ≥ n`` has label ``−1``
+and a zero image (its box carries ``i = −1``), so ``ceil(n / Bglobal)`` micro-batches visit every
+image exactly once for any ``world × B``.  :func:`crop_boxes` is the host reference of the draw.
+
+**Resample.**  Signed Q16 source coordinates (x shown; y the same with ``ch``, ``y0``):
+``step = (cw << 16) // res``; ``sx = ox·step + (step >> 1) − 32768`` clamped to
+``[0, (cw − 1) << 16]``; ``ix = sx >> 16``, ``fx = (sx >> 8) & 255``, ``ix1 = min(ix + 1, cw − 1)``;
+the source column is ``x0 + ix`` and a flipped row writes output column ``res − 1 − ox``.  The
+four-tap sum ``Σ (256 − fy | fy)(256 − fx | fx)·p`` is an integer ``≤ 255·65536 < 2²⁴``, exact in
+fp32, and the output is ``bf16_rne(fl(fl(float(sum)·sc[c]) + sh[c]))`` with
+``sc = 1 / (65536·std)``, ``sh = −mean / std`` (``mean`` / ``std`` in pixel units: 255 × the
+usual fractions, :func:`image_norm`).  At ``cw == res`` the fractions are zero: a copy.
+The resample does not antialias: store the set at ``R ≈ 8/7·res``.  :func:`image_batch_ref` is
+the host reference of the kernel (``csrc/hip/image.hip``) and the CPU trainer's path.
+
+**Placement.**  As for tokens: device-resident when ``n·R²·3`` bytes fit ``device_gb`` (one
+launch draws, resamples and stores); otherwise a worker gathers the next micro-batch's ``B``
+stored images into one of two pinned buffers (≤ 4 threads) and copies it one micro-batch ahead
+on a side stream, and the same kernel — still drawing geometry and flip itself — reads the
+staged buffer.  Both routes write identical tensors.
+"""
+
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+GATHER_THREADS = 4  # a constant: a rank shares its node's CPUs with the other ranks
+
+
+def image_norm(mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """``(sc, sh)`` of the normalise step for per-channel ``mean`` / ``std`` of pixel / 255,
+    rounded to fp32 as the kernel receives them (``sum`` carries a factor 65536)."""
+    sc = tuple(float(np.float32(1.0 / (65536.0 * 255.0 * s))) for s in std)
+    sh = tuple(float(np.float32(-m / s)) for m, s in zip(mean, std))
+    return sc, sh
+
+
+def crop_boxes(seed: int, stream: int, m: int, rank: int, B: int, n: int, R: int, res: int,
+               Bglobal: int | None = None) -> np.ndarray:
+    """The draw of micro-batch ``m`` for rows ``rank·B … rank·B + B − 1``: ``int64[B, 6]`` =
+    ``i, x0, y0, cw, ch, flip`` (``IMAGE_DOC``; ``i = −1`` past the end of the evaluation set)."""
+    import math
+    if not (8 <= res <= R <= 4096 and res % 8 == 0 and n >= 1 and B >= 1):
+        raise ValueError(f"crop_boxes: need 8 <= res <= R <= 4096, res % 8 == 0, n >= 1, B >= 1; got "
+                         f"R={R}, res={res}, n={n}, B={B}")
+    if rank < 0 or (rank + 1) * B > 1 << 32:
+        raise ValueError(f"crop_boxes: global rows rank*B + j must stay below 2^32 (rank={rank}, B={B})")
+    g = np.arange(rank * B, (rank + 1) * B, dtype=np.uint64)
+    out = np.zeros((B, 6), dtype=np.int64)
+    m32 = int(m) & _U32
+    if stream != TRAIN_STREAM:
+        Bglobal = B if Bglobal is None else int(Bglobal)
+        base = m32 * Bglobal  # a Python int: up to 2^63
+        if base < n:
+            i = base + g.astype(np.int64)
+            out[:, 0] = np.where(i < n, i, -1)
+        else:
+            out[:, 0] = -1
+        out[:, 1] = out[:, 2] = (R - res) // 2
+        out[:, 3] = out[:, 4] = res
+        return out
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    key = (seed & _U32, seed >> 32)
+    u = np.uint64
+    w0, w1, w2, _ = philox4x32_10((g, 0, int(stream), m32), key)
+    out[:, 0] = (((w1 << u(32)) | w0) % u(n)).astype(np.int64)
+    out[:, 5] = (w2 & u(1)).astype(np.int64)
+    v0, v1, v2, v3 = philox4x32_10((g, 1, int(stream), m32), key)
+    f = u(5243) + (((v0 >> u(16)) * u(60293)) >> u(16))
+    s = np.array([math.isqrt(int(x)) for x in (f * u(R * R)) << u(16)], dtype=np.uint64)
+    t = u(65536) + (((v1 >> u(16)) * u(10138)) >> u(16))
+    a, b = (s * t) >> u(32), ((s << u(16)) // t) >> u(16)
+    odd = (v1 & u(1)) == u(1)
+    cw = np.clip(np.where(odd, a, b).astype(np.int64), 1, R)
+    ch = np.clip(np.where(odd, b, a).astype(np.int64), 1, R)
+    out[:, 1] = ((v2 * (R - cw + 1).astype(np.uint64)) >> u(32)).astype(np.int64)
+    out[:, 2] = ((v3 * (R - ch + 1).astype(np.uint64)) >> u(32)).astype(np.int64)
+    out[:, 3], out[:, 4] = cw, ch
+    return out
+
+
+def _taps(c: int, res: int):
+    """``(i0, i1, f)`` int64 arrays of one axis of the resample for a crop side ``c``."""
+    step = (c << 16) // res
+    s = np.clip(np.arange(res, dtype=np.int64) * step + (step >> 1) - 32768, 0, (c - 1) << 16)
+    i0 = s >> 16
+    return i0, np.minimum(i0 + 1, c - 1), (s >> 8) & 255
+
+
+def bf16_rne_bits(x: np.ndarray) -> np.ndarray:
+    """float32 array → the int16 bit patterns of its round-to-nearest-even bf16 values."""
+    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    return (((b + 0x7FFF + ((b >> 16) & 1)) >> 16) & 0xFFFF).astype(np.uint16).view(np.int16)
+
+
+def image_batch_ref(images, labels, boxes: np.ndarray, res: int, sc, sh, staged: bool = False):
+    """Host reference of ``image_batch``: ``(x, y)`` = bf16 ``[B, res, res, 3]`` and int64 ``[B]``
+    torch tensors for the draw ``boxes`` (:func:`crop_boxes`).  ``staged``: row ``j`` reads
+    ``images[j]`` / ``labels[j]``.  ``sc`` / ``sh``: three fp32 values each (``IMAGE_DOC``)."""
+    B = boxes.shape[0]
+    sc32, sh32 = np.asarray(sc, dtype=np.float32), np.asarray(sh, dtype=np.float32)
+    x = np.zeros((B, res, res, 3), dtype=np.int16)
+    y = np.full(B, -1, dtype=np.int64)
+    for j, (i, x0, y0, cw, ch, flip) in enumerate(boxes.tolist()):
+        if i < 0:
+            continue
+        src = j if staged else i
+        y[j] = int(labels[src])
+        iy0, iy1, fy = _taps(ch, res)
+        ix0, ix1, fx = _taps(cw, res)
+        im = np.asarray(images[src][y0:y0 + ch, x0:x0 + cw]).astype(np.int64)
+        fy, fx = fy[:, None, None], fx[None, :, None]
+        top, bot = im[iy0], im[iy1]
+        tot = ((256 - fy) * ((256 - fx) * top[:, ix0] + fx * top[:, ix1])
+               + fy * ((256 - fx) * bot[:, ix0] + fx * bot[:, ix1]))
+        val = tot.astype(np.float32) * sc32 + sh32  # two fp32 roundings, as the kernel's multiply and add
+        x[j] = bf16_rne_bits(val[:, ::-1] if flip else val)
+    return torch.from_numpy(x).view(torch.bfloat16), torch.from_numpy(y)
+
+
+def open_images(path: str, res: int, classes: int):
+    """``(images, labels)`` memmaps of the directory ``path`` after the format checks."""
+    fi, fl = os.path.join(path, "images.npy"), os.path.join(path, "labels.npy")
+    images, labels = np.load(fi, mmap_mode="r"), np.load(fl, mmap_mode="r")
+    if images.dtype != np.uint8:
+        raise ValueError(f"{fi}: dtype {images.dtype}, images must be uint8")
+    if images.ndim != 4 or images.shape[3] != 3 or images.shape[0] < 1:
+        raise ValueError(f"{fi}: shape {images.shape}, images must be [n, R, R, 3] with n >= 1")
+    if images.shape[1] != images.shape[2]:
+        raise ValueError(f"{fi}: {images.shape[1]} x {images.shape[2]} images, they must be square")
+    if not images.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"{fi}: images must be stored in C order")
+    R = images.shape[1]
+    if R > 4096 or R < res or res % 8 or res < 8:
+        raise ValueError(f"{fi}: stored side R = {R} cannot feed a {res} x {res} input "
+                         f"(8 <= res <= R <= 4096 and res % 8 == 0)")
+    if labels.ndim != 1 or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError(f"{fl}: dtype {labels.dtype} shape {labels.shape}, labels must be integers [n]")
+    if labels.shape[0] != images.shape[0]:
+        raise ValueError(f"{fl}: {labels.shape[0]} labels for {images.shape[0]} images")
+    lo, hi = int(labels.min()), int(labels.max())
+    if lo < 0 or hi >= classes:
+        raise ValueError(f"{fl}: labels span [{lo}, {hi}], outside [0, {classes})")
+    return images, labels
+
+
+class ImageStream:
+    """Micro-batches of one image directory on one rank: ``batch(m, out=None) -> (x, y)``
+    with ``x`` the ``[B, 3, res, res]`` input (bf16 channels_last on a GPU) and ``y`` int64
+    ``[B]``; ``out = (xb, yb)`` are the caller's buffers (the captured step's inputs).
+    """
+    __doc__ += IMAGE_DOC
+
+    def __init__(self, path: str, B: int, res: int, classes: int, device, seed: int = 0, stream: int = TRAIN_STREAM,
+                 rank: int = 0, world: int = 1, device_gb: float = 8.0, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        self.path, self.B, self.res, self.classes = str(path), int(B), int(res), int(classes)
+        self.device = torch.device(device)
+        self.seed, self.stream, self.rank = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(rank)
+        self.Bglobal = int(world) * self.B
+        if rank < 0 or rank >= world or self.Bglobal > 1 << 31:
+            raise ValueError(f"need 0 <= rank < world and world*B <= 2^31 (rank={rank}, world={world}, B={B})")
+        self.images, self.labels = open_images(self.path, self.res, self.classes)
+        self.n, self.R = int(self.images.shape[0]), int(self.images.shape[1])
+        self.norm = image_norm(mean, std)
+        self.set = self.lab = None
+        self._pool = None
+        if self.device.type == "cuda":
+            self._hip = _native.require_hip()
+            if self.n * self.R * self.R * 3 <= device_gb * 2**30:
+                # uploaded in pieces of about 256 MiB, so the host never holds a second copy of the file
+                self.set = torch.empty((self.n, self.R, self.R, 3), dtype=torch.uint8, device=self.device)
+                per = max(1, (256 << 20) // (self.R * self.R * 3))
+                for o in range(0, self.n, per):
+                    self.set[o:o + per].copy_(torch.from_numpy(np.array(self.images[o:o + per])))
+                self.lab = torch.from_numpy(np.asarray(self.labels).astype(np.int32)).to(self.device)
+            else:
+                self._init_staging()
+        self.placement = "cpu" if self.device.type != "cuda" else ("device" if self.set is not None else "host")
+
+    def batches_per_epoch(self) -> int:
+        """Micro-batches of the evaluation stream that cover the file once: ``ceil(n / (world·B))``."""
+        return -(-self.n // self.Bglobal)
+
+    # -- host side ----------------------------------------------------------
+    def boxes(self, m: int) -> np.ndarray:
+        return crop_boxes(self.seed, self.stream, m, self.rank, self.B, self.n, self.R, self.res, self.Bglobal)
+
+    def host_batch(self, m: int):
+        """``(x, y)`` of micro-batch ``m`` built with numpy (bf16 NHWC, int64): the reference of
+        both GPU routes and the CPU trainer's path."""
+        return image_batch_ref(self.images, self.labels, self.boxes(m), self.res, *self.norm)
+
+    def _gather(self, idx, img_out: np.ndarray, lab_out: np.ndarray, pool=None):
+        """Stored images ``idx`` (−1: past the end, left as they are) into ``img_out`` / ``lab_out``."""
+        def part(rows):
+            for r in rows:
+                if idx[r] >= 0:
+                    img_out[r] = self.images[idx[r]]
+                    lab_out[r] = self.labels[idx[r]]
+        chunks = [range(k, len(idx), GATHER_THREADS) for k in range(GATHER_THREADS)]
+        if pool is None:
+            part(range(len(idx)))
+            return
+        futs = [pool.submit(part, c) for c in chunks[1:]]
+        part(chunks[0])
+        for f in futs:
+            f.result()
+
+    # -- host-staged route --------------------------------------------------
+    def _init_staging(self):
+        import concurrent.futures as cf
+        shape = (self.B, self.R, self.R, 3)
+        self._pinned = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._pinned_lab = [torch.zeros(self.B, dtype=torch.int32).pin_memory() for _ in range(2)]
+        self._staged = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self._staged_lab = [torch.zeros(self.B, dtype=torch.int32, device=self.device) for _ in range(2)]
+        self._consumed = [None, None]  # compute-stream events: the kernel has read staged[k]
+        self._side = torch.cuda.Stream(self.device)
+        # one staging task at a time; it gathers a share itself and hands the rest to the other workers
+        self._pool = cf.ThreadPoolExecutor(max_workers=GATHER_THREADS, thread_name_prefix="pdo-data")
+        self._next = None  # (m, future) of the micro-batch on its way
+        self._slot = 0
+
+    def _stage(self, m: int, k: int, consumed):
+        """Worker thread: gather micro-batch ``m`` into pinned buffers ``k`` and copy them to the
+        staged buffers ``k`` on the side stream (the event discipline of ``TokenStream._stage``)."""
+        self._gather(self.boxes(m)[:, 0], self._pinned[k].numpy(), self._pinned_lab[k].numpy(), self._pool)
+        with torch.cuda.stream(self._side):
+            if consumed is not None:
+                self._side.wait_event(consumed)
+            self._staged[k].copy_(self._pinned[k], non_blocking=True)
+            self._staged_lab[k].copy_(self._pinned_lab[k], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._side)
+        ev.synchronize()  # this thread only: the pinned buffers may be rewritten two micro-batches on
+        return k, ev
+
+    def _submit(self, m: int):
+        k = self._slot
+        self._slot ^= 1
+        self._next = (m, self._pool.submit(self._stage, m, k, self._consumed[k]))
+
+    def _staged_batch(self, m: int, xb, yb):
+        if self._next is None or self._next[0] != m:
+            if self._next is not None:
+                self._next[1].result()  # a jump in m (resume, evaluation restart): drop what was on its way
+            self._submit(m)
+        k, ev = self._next[1].result()
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ev)
+        out = self._launch(self._staged[k], self._staged_lab[k], m, True, xb, yb)
+        done = torch.cuda.Event()
+        done.record(cur)
+        self._consumed[k] = done
+        self._submit(m + 1)
+        return out
+
+    def _launch(self, img, lab, m, staged, xb, yb):
+        return self._hip.image_batch(img, lab, self.n, self.B, self.R, self.res, self.norm,
+                                     (self.seed, self.stream, int(m) & _U32, self.rank), self.Bglobal, staged, xb, yb)
+
+    # -- API ------------------------------------------------------------------
+    def batch(self, m: int, out=None):
+        xb, yb = out if out is not None else (None, None)
+        direct = (xb is None or (xb.is_cuda and xb.dtype == torch.bfloat16 and xb.is_contiguous()
+                                 and tuple(xb.shape) == (self.B, self.res, self.res, 3)))
+        if self.device.type == "cuda":
+            tx = xb if direct else None
+            x, y = (self._launch(self.set, self.lab, m, False, tx, yb) if self.set is not None
+                    else self._staged_batch(m, tx, yb))
+        else:
+            x, y = self.host_batch(m)
+            if yb is not None:
+                yb.copy_(y)
+                y = yb
+        x = x.permute(0, 3, 1, 2)  # NHWC memory: a channels_last [B, 3, res, res]
+        if xb is not None and not direct:  # an NCHW / fp32 buffer (the CPU trainer): one converting copy
+            xb.copy_(x)
+            x = xb
+        return x, y
+
+    def close(self):
+        if self._pool is not None:
+            if self._next is not None:
+                self._next[1].result()
             self._pool.shutdown(wait=True)
             self._pool = None
             self._next = None

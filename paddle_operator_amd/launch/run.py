@@ -46,26 +46,34 @@ def parse_args(argv=None):
                          "default 0)")
     ap.add_argument("--dropout-seed", type=int, default=0, help="gpt2: seed of the dropout masks")
     ap.add_argument("--data", default=os.environ.get("PDO_TRAIN_DATA", ""),
-                    help="gpt2: training token file, raw little-endian uint16 ids (nanoGPT train.bin); default: "
-                         "synthetic batches")
+                    help="gpt2: training token file, raw little-endian uint16 ids (nanoGPT train.bin); resnet50: "
+                         "directory with images.npy (uint8 [n, R, R, 3]) and labels.npy ([n]); default: synthetic "
+                         "batches")
     ap.add_argument("--val-data", default=os.environ.get("PDO_VAL_DATA", ""),
-                    help="gpt2: held-out token file of the same format (--eval-every)")
-    ap.add_argument("--data-seed", type=int, default=0, help="gpt2: 64-bit seed of the window sampler")
+                    help="gpt2 / resnet50: held-out token file / image directory of the same format (--eval-every)")
+    ap.add_argument("--data-seed", type=int, default=0,
+                    help="gpt2 / resnet50: 64-bit seed of the window / crop sampler")
     ap.add_argument("--data-device-gb", type=float, default=8.0,
-                    help="gpt2: a token file up to this size is held in GPU memory; a larger one is read from the "
-                         "host one micro-batch ahead")
+                    help="gpt2 / resnet50: a token file / image set up to this size is held in GPU memory; a larger "
+                         "one is read from the host one micro-batch ahead")
     ap.add_argument("--grad-accum", type=int, default=None,
                     help="gpt2: micro-batches per optimizer step (default 1); --steps counts optimizer steps")
-    ap.add_argument("--lr", type=float, default=3e-4, help="gpt2: peak learning rate")
+    ap.add_argument("--lr", type=float, default=None,
+                    help="gpt2 / resnet50: peak learning rate (default 3e-4 / 0.1)")
     ap.add_argument("--lr-schedule", choices=["constant", "cosine"], default=None,
-                    help="gpt2: constant (default) or linear warmup + cosine decay")
-    ap.add_argument("--lr-warmup", type=int, default=0, help="gpt2: warmup optimizer steps of --lr-schedule cosine")
+                    help="gpt2 / resnet50: constant (default) or linear warmup + cosine decay")
+    ap.add_argument("--lr-warmup", type=int, default=0,
+                    help="gpt2 / resnet50: warmup optimizer steps of --lr-schedule cosine")
     ap.add_argument("--lr-decay-steps", type=int, default=0,
-                    help="gpt2: optimizer step at which the cosine reaches its floor (default --steps)")
-    ap.add_argument("--lr-min-ratio", type=float, default=0.1, help="gpt2: floor of the cosine as a fraction of --lr")
+                    help="gpt2 / resnet50: optimizer step at which the cosine reaches its floor (default --steps)")
+    ap.add_argument("--lr-min-ratio", type=float, default=0.1,
+                    help="gpt2 / resnet50: floor of the cosine as a fraction of --lr")
     ap.add_argument("--eval-every", type=int, default=0,
-                    help="gpt2: held-out loss on --val-data every N optimizer steps (PDO_EVAL records)")
-    ap.add_argument("--eval-batches", type=int, default=8, help="gpt2: micro-batches per rank of one evaluation")
+                    help="gpt2: held-out loss, resnet50: held-out loss / top-1 / top-5, on --val-data every N "
+                         "optimizer steps (PDO_EVAL records)")
+    ap.add_argument("--eval-batches", type=int, default=None,
+                    help="micro-batches per rank of one evaluation (gpt2: default 8; resnet50: default 0 = the "
+                         "whole set once)")
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="resnet50: keep the step eager (default on one GPU rank: captured once into a HIP graph "
                          "and replayed, workloads/resnet.py; multi-rank steps stay eager)")
@@ -87,6 +95,11 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.eval_every and not args.val_data:
         ap.error("--eval-every needs --val-data (or PDO_VAL_DATA)")
+    args.lr_given = args.lr is not None  # the records carry only flags that were given
+    if args.lr is None:
+        args.lr = 0.1 if args.workload == "resnet50" else 3e-4
+    if args.eval_batches is None:
+        args.eval_batches = 0 if args.workload == "resnet50" else 8
     return args
 
 
@@ -134,7 +147,11 @@ def run_collective(args, jenv) -> int:
         tokens_per_step = trainer.tokens_per_step()
     elif args.workload == "resnet50":
         from ..workloads.resnet import ResNetTrainer
-        trainer = ResNetTrainer(args.batch or (4 if args.tiny else 256), dev, tiny=args.tiny, graph=args.graph)
+        trainer = ResNetTrainer(args.batch or (4 if args.tiny else 256), dev, tiny=args.tiny, graph=args.graph,
+                                lr=args.lr, lr_schedule=args.lr_schedule, lr_warmup=args.lr_warmup,
+                                lr_decay_steps=args.lr_decay_steps or args.steps, lr_min_ratio=args.lr_min_ratio,
+                                data=args.data or None, val_data=args.val_data or None, data_seed=args.data_seed,
+                                data_device_gb=args.data_device_gb)
         trainer.sync_initial_weights()
         tokens_per_step = trainer.B  # images
     start_step = 0
@@ -169,7 +186,8 @@ def run_collective(args, jenv) -> int:
     last = t0
     done = 0
     gpt2 = args.workload == "gpt2"
-    evaluating = gpt2 and args.eval_every > 0 and bool(args.val_data)
+    resnet = args.workload == "resnet50"
+    evaluating = (gpt2 or resnet) and args.eval_every > 0 and bool(args.val_data)
     val_loss = None
     while step < args.steps:
         in_step[0] = True
@@ -187,9 +205,12 @@ def run_collective(args, jenv) -> int:
                 ckpt.save(state(), args.ckpt_dir, step)
         if evaluating and step % args.eval_every == 0:
             with trace.range("evaluate"):
-                val_loss = trainer.evaluate(args.eval_batches)  # every rank: one all-reduce inside
+                val = trainer.evaluate(args.eval_batches)  # every rank: one all-reduce inside
+            # gpt2: the loss; resnet50: {"val_loss", "top1", "top5", "images"}
+            val_loss = val["val_loss"] if resnet else val
             if b.rank == 0:
-                print("PDO_EVAL " + json.dumps({"step": step, "val_loss": val_loss}), flush=True)
+                print("PDO_EVAL " + json.dumps({"step": step, **val} if resnet else {"step": step, "val_loss": val}),
+                      flush=True)
         if step % args.log_every == 0 or step == args.steps:
             if dev.type == "cuda":
                 torch.cuda.synchronize(dev)
@@ -206,6 +227,7 @@ def run_collective(args, jenv) -> int:
     dt = time.perf_counter() - t0
     if gpt2:
         trainer.check_data()
+    if gpt2 or resnet:
         trainer.close()
     if args.ckpt_dir and b.rank == 0:
         ckpt.save(state(), args.ckpt_dir, step)
@@ -216,8 +238,10 @@ def run_collective(args, jenv) -> int:
         summary["dropout"] = args.dropout
         summary["attn_dropout"] = args.attn_dropout
         summary.update(_gpt2_flags(args))
-        if val_loss is not None:
-            summary["val_loss"] = val_loss
+    if resnet:
+        summary.update(_resnet_flags(args))
+    if val_loss is not None:
+        summary["val_loss"] = val_loss
     print("PDO_DONE " + json.dumps(summary), flush=True)
     if dist.is_initialized():
         dist.barrier()
@@ -233,6 +257,19 @@ def _gpt2_flags(args) -> dict:
         out["data"] = args.data
     if args.grad_accum is not None:
         out["grad_accum"] = args.grad_accum
+    if args.lr_schedule is not None:
+        out["lr_schedule"] = args.lr_schedule
+    return out
+
+
+def _resnet_flags(args) -> dict:
+    """The image-data / schedule flags that were given to a resnet50 run, for its PDO_DONE
+    and PDO_BENCH records (absent keys: the flag was not given)."""
+    out = {}
+    if args.data:
+        out["data"] = args.data
+    if args.lr_given:
+        out["lr"] = args.lr
     if args.lr_schedule is not None:
         out["lr_schedule"] = args.lr_schedule
     return out
@@ -282,6 +319,8 @@ def _bench(args, b, jenv, trainer, tokens_per_step, ready_rec) -> int:
         res["dropout"] = args.dropout  # 0.0: the headline is a dropout-free step
         res["attn_dropout"] = args.attn_dropout
         res.update(_gpt2_flags(args))
+    if args.workload == "resnet50":
+        res.update(_resnet_flags(args))
     if dev.type == "cuda":
         res["gpu_name"] = torch.cuda.get_device_name(dev)
         res["max_mem_gb"] = round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)

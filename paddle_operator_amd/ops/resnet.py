@@ -189,12 +189,60 @@ def _apply_bitmask(t, mask):
 _BN_FUSED = [True]
 _BN_LINK = [True]
 
+# ----------------------------------------------------------------------------
+# Inference (bn.eval(), no autograd): BatchNorm from the running statistics on
+# the same apply kernels (batchnorm.hip bn_eval_ss → scale | shift rows), behind
+# the hand-written convolutions without their statistics epilogue
+# ----------------------------------------------------------------------------
+_EVAL_USED = [0]  # BatchNorms applied from their running statistics by the HIP eval kernels (tests)
+
+
+def _bn_eval_mode(bn: torch.nn.BatchNorm2d) -> bool:
+    """``bn`` normalises with its running statistics and nothing records a backward."""
+    return (not bn.training and _BN_FUSED[0] and not torch.is_grad_enabled() and bn.weight is not None
+            and bn.weight.dtype == torch.float32 and bn.running_mean is not None)
+
+
+def _bn_eval_ok(bn: torch.nn.BatchNorm2d, x, residual=None) -> bool:
+    """``bn`` in eval mode can run ``x`` (+ residual) on the HIP inference kernels."""
+    return (_bn_eval_mode(bn) and use_hip(x)
+            and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[1] % 8 == 0
+            and x.is_contiguous(memory_format=torch.channels_last)
+            and (residual is None or (residual.dtype == torch.bfloat16 and residual.shape == x.shape
+                                      and residual.is_contiguous(memory_format=torch.channels_last))))
+
+
+def _bn_eval(bn: torch.nn.BatchNorm2d, x, relu: bool, residual=None):
+    _EVAL_USED[0] += 1
+    return _native.require_hip().bn_act_eval(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                             bn.eps, relu)
+
+
+def _shadow_weight(w):
+    """The bf16 channels_last operand of a convolution weight: the arena's shadow while it
+    is live (FlatParams.shadow_scope), else one cast."""
+    sh = getattr(w, "_pdo_shadow", None)
+    if sh is not None and sh[0].shadow_live and sh[1].dtype == torch.bfloat16 \
+            and sh[1].is_contiguous(memory_format=torch.channels_last):
+        return sh[1]
+    return w.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+
+
+def _conv_eval(conv: torch.nn.Conv2d, x, stem: bool):
+    """``conv(x)`` on the hand-written kernels, forward only, no statistics epilogue."""
+    if stem:
+        return _native.require_hip().stem_fwd(x, _shadow_weight(conv.weight), False)[0]
+    return _ConvFn.apply(x, conv.weight, conv.stride[0], conv.padding[0], False)[0]
+
 
 def bn_act(bn: torch.nn.BatchNorm2d, x, relu: bool = True, residual=None, rlink=None, mlink=None):
     """Training BatchNorm → (+ residual) → ReLU in one HIP forward pass over the
     activation (plus a statistics pass), and one backward pass (plus stats).
-    Falls back to PyTorch ops outside the fused case (eval mode, CPU, NCHW,
-    C % 8 != 0)."""
+    In eval mode (no autograd) the same apply kernel runs from the running
+    statistics (_bn_eval).  Falls back to PyTorch ops outside these cases (CPU,
+    NCHW, C % 8 != 0)."""
+    if _bn_eval_ok(bn, x, residual):
+        return _bn_eval(bn, x, relu, residual)
     fused = (_BN_FUSED[0] and use_hip(x) and bn.training and x.dtype == torch.bfloat16 and x.dim() == 4
              and x.is_contiguous(memory_format=torch.channels_last) and x.shape[1] % 8 == 0
              and bn.weight is not None and bn.weight.dtype == torch.float32
@@ -504,7 +552,16 @@ def _conv_bn_act(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, x, relu: bool 
     BatchNorm statistics taken in the implicit GEMM's epilogue where that kernel
     runs the forward; otherwise the framework convolution + ops.bn_act.
     ``fork``: returns (out, x_alias) — x for a second consumer whose gradient
-    then joins this convolution's dX in its epilogue (_ConvFn)."""
+    then joins this convolution's dX in its epilogue (_ConvFn).  Eval mode: the
+    same convolution without its statistics epilogue + the BatchNorm from its
+    running statistics (_bn_eval)."""
+    if _bn_eval_mode(bn):
+        estem = not fork and _stem_ok(conv, x)
+        if estem or _hip_conv_ok(conv, x):
+            y = _conv_eval(conv, x, estem)
+            if _bn_eval_ok(bn, y, residual):
+                out = _bn_eval(bn, y, relu, residual)
+                return (out, x) if fork else out
     stem = not fork and _stem_ok(conv, x)
     if (stem or _hip_conv_ok(conv, x)) and _bn_fused_ok(bn, residual):
         rl = _ResMaskLink() if (fork and _RES_MASK[0] and torch.is_grad_enabled()) else None
@@ -594,7 +651,16 @@ def conv_bn_ds_act(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, x, dconv: to
     Both convolutions on the hand-written kernels with BatchNorm statistics in
     their epilogues, then one apply pass (_BNActBNResFn); otherwise the
     downsample branch through conv_bn_act(as_residual=True) and bn3 with it as
-    the residual."""
+    the residual.  Eval mode: both BatchNorms from their running statistics in
+    the same single apply pass (bn_act_eval_pair)."""
+    if (_DS_FUSED[0] and _bn_eval_mode(bn) and _bn_eval_mode(dbn) and _hip_conv_ok(conv, x)
+            and _hip_conv_ok(dconv, xa)):
+        yd, y = _conv_eval(dconv, xa, False), _conv_eval(conv, x, False)
+        if _bn_eval_ok(bn, y, yd):
+            _EVAL_USED[0] += 2
+            return _native.require_hip().bn_act_eval_pair(y, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                                          bn.eps, yd, dbn.weight, dbn.bias, dbn.running_mean,
+                                                          dbn.running_var, dbn.eps, True)
     m = _native.require_hip() if use_hip(x) else None
     if (m is not None and _DS_FUSED[0] and torch.is_grad_enabled() and _hip_conv_ok(conv, x)
             and _hip_conv_ok(dconv, xa) and _bn_fused_ok(bn, None) and _bn_fused_ok(dbn, None)):
@@ -681,7 +747,14 @@ _STEM_POOL = [True]
 def conv_bn_relu_maxpool(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, x):
     """ResNet stem: max_pool_3x3s2(ReLU(BN(conv(x)))) — the space-to-depth stem
     convolution (_StemFn) with the BatchNorm, ReLU and max-pool fused into one
-    pass each way (_BNReluPoolFn) on the HIP path; else conv_bn_act + max-pool."""
+    pass each way (_BNReluPoolFn) on the HIP path; else conv_bn_act + max-pool.
+    Eval mode: the stem convolution, then BatchNorm (running statistics) + ReLU +
+    max-pool in one pass that writes only the pooled activation."""
+    if (_STEM_POOL[0] and _bn_eval_mode(bn) and _stem_ok(conv, x)
+            and conv.out_channels % 8 == 0 and 256 % (conv.out_channels // 8) == 0):
+        y = _conv_eval(conv, x, True)
+        _EVAL_USED[0] += 1
+        return _native.require_hip().bn_relu_pool_eval(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
     if _STEM_POOL[0] and _stem_ok(conv, x) and _bn_fused_ok(bn, None):
         y, st = _StemFn.apply(x, conv.weight)
         mom = bn.momentum if bn.momentum is not None else 0.1
