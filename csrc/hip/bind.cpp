@@ -6,6 +6,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/extension.h>
 
+#include <climits>
 #include <cmath>
 
 #include "gemm_nt_epi.h"
@@ -360,6 +361,65 @@ at::Tensor embed_bwd_sorted(at::Tensor dy, at::Tensor keys, at::Tensor perm, at:
   CHECK_RC(pdo::embed_bwd_sorted(bp(dy), keys.data_ptr<int64_t>(), perm.data_ptr<int64_t>(), bp(dwte), bp(dwpe),
                                  fp(part), B, S, C, (int)dwte.size(0), (int)P, 1, cur_stream()), "embed_bwd_sorted");
   return dwpe;
+}
+
+// ---------------------------------------------------------------- CTR sparse side
+#define CHECK_ALIGN16(t) TORCH_CHECK(reinterpret_cast<uintptr_t>((t).data_ptr()) % 16 == 0, #t " must be 16-B aligned")
+
+// (X[B, ldx], wide_sum[B], fm[B], ssum[B, D]); fm and ssum are empty tensors without `fm`
+std::vector<at::Tensor> ctr_fwd(at::Tensor ids, at::Tensor dense, at::Tensor deep, at::Tensor wide, int64_t ldx,
+                                bool fm) {
+  CHECK_IN(ids); CHECK_IN(dense); CHECK_IN(deep); CHECK_IN(wide);
+  CHECK_I64(ids); CHECK_F32(dense); CHECK_F32(deep); CHECK_F32(wide); CHECK_ALIGN16(deep);
+  TORCH_CHECK(ids.dim() == 2 && dense.dim() == 2 && dense.size(0) == ids.size(0) && deep.dim() == 2 &&
+              wide.numel() == deep.size(0), "ctr_fwd: ids [B, S], dense [B, n_dense], deep [rows, D], wide [rows]");
+  const int64_t B = ids.size(0), S = ids.size(1), D = deep.size(1), nd = dense.size(1);
+  TORCH_CHECK(B * S <= INT_MAX && ldx >= S * D + nd && ldx <= INT_MAX, "ctr_fwd: ldx < S*D + n_dense");
+  auto X = at::empty({B, ldx}, deep.options());
+  auto ws = at::empty({B}, deep.options());
+  auto fmt = at::empty({fm ? B : 0}, deep.options());
+  auto ssum = at::empty({fm ? B : 0, D}, deep.options());
+  CHECK_RC(pdo::ctr_fwd(ids.data_ptr<int64_t>(), fp(dense), fp(deep), fp(wide), fp(X), fp(ws),
+                        fm ? fp(ssum) : nullptr, fm ? fp(fmt) : nullptr, (int)B, (int)S, (int)D, (int)nd, (int)ldx,
+                        (long long)deep.size(0), cur_stream()), "ctr_fwd");
+  return {X, ws, fmt, ssum};
+}
+
+// mode 0 (GRAD): out_deep / out_wide receive the summed gradient rows of the batch's ids;
+// mode 1 (ADAGRAD): they are the accumulators, deep / wide are updated, lr is a device float
+void ctr_bwd_rows(at::Tensor keys, at::Tensor perm, at::Tensor dX, at::Tensor dlogit,
+                  c10::optional<at::Tensor> ssum, int64_t S, at::Tensor deep, at::Tensor wide, at::Tensor out_deep,
+                  at::Tensor out_wide, c10::optional<at::Tensor> lr, int64_t mode) {
+  CHECK_IN(keys); CHECK_IN(perm); CHECK_DEV(dX); CHECK_IN(dlogit); CHECK_IN(deep); CHECK_IN(wide);
+  CHECK_IN(out_deep); CHECK_IN(out_wide);
+  CHECK_I64(keys); CHECK_I64(perm); CHECK_F32(dX); CHECK_F32(dlogit); CHECK_F32(deep); CHECK_F32(wide);
+  CHECK_F32(out_deep); CHECK_F32(out_wide); CHECK_ALIGN16(deep); CHECK_ALIGN16(out_deep);
+  TORCH_CHECK(dX.dim() == 2 && deep.dim() == 2 && S >= 1, "ctr_bwd_rows: dX [B, >= S*D], deep [rows, D]");
+  const int64_t B = dX.size(0), D = deep.size(1), rows = deep.size(0);
+  const int64_t ldx = B > 1 ? dX.stride(0) : dX.size(1);
+  TORCH_CHECK((dX.size(1) == 1 || dX.stride(1) == 1) && dX.size(1) >= S * D && ldx >= dX.size(1) && ldx <= INT_MAX,
+              "ctr_bwd_rows: dX rows must be contiguous and hold S*D columns");
+  TORCH_CHECK(ldx % 4 != 0 || reinterpret_cast<uintptr_t>(dX.data_ptr()) % 16 == 0, "dX must be 16-B aligned");
+  TORCH_CHECK(B * S <= INT_MAX && keys.numel() == B * S && perm.numel() == B * S && dlogit.numel() == B,
+              "ctr_bwd_rows: keys, perm [B*S], dlogit [B]");
+  TORCH_CHECK(wide.numel() == rows && out_deep.dim() == 2 && out_deep.size(0) == rows && out_deep.size(1) == D &&
+              out_wide.numel() == rows, "ctr_bwd_rows: table shapes");
+  const float* ss = nullptr;
+  if (ssum.has_value()) {
+    CHECK_IN(*ssum); CHECK_F32(*ssum); CHECK_ALIGN16(*ssum);
+    TORCH_CHECK(ssum->dim() == 2 && ssum->size(0) == B && ssum->size(1) == D, "ctr_bwd_rows: ssum [B, D]");
+    ss = fp(*ssum);
+  }
+  const float* lrp = nullptr;
+  if (lr.has_value()) {
+    CHECK_IN(*lr); CHECK_F32(*lr);
+    TORCH_CHECK(lr->numel() == 1, "ctr_bwd_rows: lr is one device float");
+    lrp = fp(*lr);
+  }
+  auto part = at::empty({(int64_t)pdo::ctr_part_floats(B * S, (int)D)}, deep.options());
+  CHECK_RC(pdo::ctr_bwd_rows(keys.data_ptr<int64_t>(), perm.data_ptr<int64_t>(), fp(dX), fp(dlogit), ss, fp(part),
+                             fp(deep), fp(wide), fp(out_deep), fp(out_wide), lrp, (int)B, (int)S, (int)D, (int)ldx,
+                             (long long)rows, (int)mode, cur_stream()), "ctr_bwd_rows");
 }
 
 // ---------------------------------------------------------------- optimizer
@@ -1598,6 +1658,8 @@ PYBIND11_MODULE(_pdo_hip, m) {
         py::arg("seed") = 0, py::arg("site") = 0, py::arg("step") = 0, py::arg("offset") = 0);
   m.def("embed_bwd", &embed_bwd);
   m.def("embed_bwd_sorted", &embed_bwd_sorted);
+  m.def("ctr_fwd", &ctr_fwd);
+  m.def("ctr_bwd_rows", &ctr_bwd_rows);
   m.def("sumsq", &sumsq);
   m.def("sumsq_chunks", &sumsq_chunks);
   m.def("set_adamw_variant", [](int v) { pdo::adamw_set_variant(v); });

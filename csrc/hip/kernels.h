@@ -260,6 +260,22 @@ int sgd_flat(float* w, const float* g, float* buf, const float* decay_chunks, lo
 // under a captured step, where a by-value argument is frozen at capture
 int cast_f32_bf16(const float* in, bf16* out, long long n, hipStream_t st);
 
+// ctr.hip: the CTR models' sparse side; fp32 tables, D % 4 == 0 and 4 <= D <= 64 or -2
+// (sum orders and rounding counts: the file's header)
+enum { CTR_GRAD = 0, CTR_ADAGRAD = 1 };
+// X[B, ldx] = [S gathered deep rows | n_dense dense features | zeros]; wide_sum[B];
+// ssum[B, D] and fm[B] both given (DeepFM) or both null
+int ctr_fwd(const int64_t* ids, const float* dense, const float* deep, const float* wide, float* X, float* wide_sum,
+            float* ssum, float* fm, int B, int S, int D, int n_dense, int ldx, long long rows, hipStream_t st);
+// part: ctr_part_floats(B·S, D) fp32 scratch (partials of runs that cross segments)
+long long ctr_part_floats(long long N, int D);
+// keys / perm: the B·S ids sorted stably and their flat indices; ssum null = no fm term.
+// CTR_GRAD: out_deep / out_wide are the gradient rows; CTR_ADAGRAD: they are the
+// accumulators and deep / wide are updated in place at the rate *lr (a device float)
+int ctr_bwd_rows(const int64_t* keys, const int64_t* perm, const float* dX, const float* dlogit, const float* ssum,
+                 float* part, float* deep, float* wide, float* out_deep, float* out_wide, const float* lr, int B,
+                 int S, int D, int ldx, long long rows, int mode, hipStream_t st);
+
 // optim.hip
 int sumsq(const bf16* g, long long n, float* part, int part_cap, float scale, float* out, hipStream_t st);
 void adamw_set_variant(int v);

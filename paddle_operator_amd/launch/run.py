@@ -8,6 +8,7 @@ images (deploy/examples/resnet.yaml:14-19).
 
     python -m paddle_operator_amd.launch --workload gpt2 --model gpt2-medium --steps 100
     python -m paddle_operator_amd.launch --workload wide_deep --steps 200      # PS mode from env
+    python -m paddle_operator_amd.launch --workload deepfm --steps 200         # no pservers: on the GPU
     python -m paddle_operator_amd.launch --workload resnet50 --elastic         # elastic agent
 """
 from __future__ import annotations
@@ -36,7 +37,9 @@ def parse_args(argv=None):
     ap.add_argument("--dump-outputs", default="",
                     help="--bench: after the timed steps write what the last step computed (loss, and a fixed seeded "
                          "sample of the updated parameters and of the gradients) as <dir>/<name>.npy")
-    ap.add_argument("--batch", type=int, default=0, help="per-rank micro batch (0 = workload default)")
+    ap.add_argument("--batch", type=int, default=0,
+                    help="per-rank micro batch (0 = workload default; wide_deep / deepfm without pservers: 4096, "
+                         "64 with --tiny)")
     ap.add_argument("--seq", type=int, default=1024)
     ap.add_argument("--tiny", action="store_true", help="tiny model variant (CPU tests)")
     ap.add_argument("--dropout", type=float, default=0.0,
@@ -52,14 +55,18 @@ def parse_args(argv=None):
     ap.add_argument("--val-data", default=os.environ.get("PDO_VAL_DATA", ""),
                     help="gpt2 / resnet50: held-out token file / image directory of the same format (--eval-every)")
     ap.add_argument("--data-seed", type=int, default=0,
-                    help="gpt2 / resnet50: 64-bit seed of the window / crop sampler")
+                    help="gpt2 / resnet50: 64-bit seed of the window / crop sampler; wide_deep / deepfm: seed of "
+                         "the synthetic batches")
     ap.add_argument("--data-device-gb", type=float, default=8.0,
                     help="gpt2 / resnet50: a token file / image set up to this size is held in GPU memory; a larger "
                          "one is read from the host one micro-batch ahead")
     ap.add_argument("--grad-accum", type=int, default=None,
                     help="gpt2: micro-batches per optimizer step (default 1); --steps counts optimizer steps")
     ap.add_argument("--lr", type=float, default=None,
-                    help="gpt2 / resnet50: peak learning rate (default 3e-4 / 0.1)")
+                    help="gpt2 / resnet50: peak learning rate (default 3e-4 / 0.1); wide_deep / deepfm without "
+                         "pservers: the tower's Adam rate (default 1e-3)")
+    ap.add_argument("--sparse-lr", type=float, default=0.05,
+                    help="wide_deep / deepfm without pservers: the tables' row-wise Adagrad rate")
     ap.add_argument("--lr-schedule", choices=["constant", "cosine"], default=None,
                     help="gpt2 / resnet50: constant (default) or linear warmup + cosine decay")
     ap.add_argument("--lr-warmup", type=int, default=0,
@@ -70,7 +77,8 @@ def parse_args(argv=None):
                     help="gpt2 / resnet50: floor of the cosine as a fraction of --lr")
     ap.add_argument("--eval-every", type=int, default=0,
                     help="gpt2: held-out loss, resnet50: held-out loss / top-1 / top-5, on --val-data every N "
-                         "optimizer steps (PDO_EVAL records)")
+                         "optimizer steps (PDO_EVAL records); wide_deep / deepfm without pservers: held-out "
+                         "log-loss and AUC on a synthetic validation stream, no --val-data needed")
     ap.add_argument("--eval-batches", type=int, default=None,
                     help="micro-batches per rank of one evaluation (gpt2: default 8; resnet50: default 0 = the "
                          "whole set once)")
@@ -93,11 +101,12 @@ def parse_args(argv=None):
     ap.add_argument("--timeout", type=int, default=300)
     ap.add_argument("--throttle-ms", type=float, default=0.0, help=argparse.SUPPRESS)  # tests: stretch steps
     args = ap.parse_args(argv)
-    if args.eval_every and not args.val_data:
+    ctr = args.workload in ("wide_deep", "deepfm")
+    if args.eval_every and not args.val_data and not ctr:
         ap.error("--eval-every needs --val-data (or PDO_VAL_DATA)")
     args.lr_given = args.lr is not None  # the records carry only flags that were given
     if args.lr is None:
-        args.lr = 0.1 if args.workload == "resnet50" else 3e-4
+        args.lr = 0.1 if args.workload == "resnet50" else 1e-3 if ctr else 3e-4
     if args.eval_batches is None:
         args.eval_batches = 0 if args.workload == "resnet50" else 8
     return args
@@ -154,6 +163,15 @@ def run_collective(args, jenv) -> int:
                                 data_device_gb=args.data_device_gb)
         trainer.sync_initial_weights()
         tokens_per_step = trainer.B  # images
+    elif args.workload in ("wide_deep", "deepfm"):  # no pserver endpoints (main()): the GPU trainer
+        from ..models.wide_deep import WideDeepConfig
+        from ..workloads.ctr import CTRTrainer
+        cfg = (WideDeepConfig(vocab_per_slot=1000, model=args.workload) if args.tiny
+               else WideDeepConfig(model=args.workload))
+        trainer = CTRTrainer(cfg, args.batch or (64 if args.tiny else 4096), dev, lr=args.lr,
+                             sparse_lr=args.sparse_lr, data_seed=args.data_seed)
+        trainer.sync_initial_weights()
+        tokens_per_step = trainer.B  # samples
     start_step = 0
     if trainer is not None and args.ckpt_dir:
         st, start_step = ckpt.load_latest(args.ckpt_dir)
@@ -187,7 +205,8 @@ def run_collective(args, jenv) -> int:
     done = 0
     gpt2 = args.workload == "gpt2"
     resnet = args.workload == "resnet50"
-    evaluating = (gpt2 or resnet) and args.eval_every > 0 and bool(args.val_data)
+    ctr = args.workload in ("wide_deep", "deepfm")
+    evaluating = args.eval_every > 0 and (ctr or (gpt2 or resnet) and bool(args.val_data))
     val_loss = None
     while step < args.steps:
         in_step[0] = True
@@ -206,11 +225,11 @@ def run_collective(args, jenv) -> int:
         if evaluating and step % args.eval_every == 0:
             with trace.range("evaluate"):
                 val = trainer.evaluate(args.eval_batches)  # every rank: one all-reduce inside
-            # gpt2: the loss; resnet50: {"val_loss", "top1", "top5", "images"}
-            val_loss = val["val_loss"] if resnet else val
+            # gpt2: the loss; resnet50: {"val_loss", "top1", "top5", "images"}; ctr: {"val_loss", "auc"}
+            val_loss = val["val_loss"] if resnet or ctr else val
             if b.rank == 0:
-                print("PDO_EVAL " + json.dumps({"step": step, **val} if resnet else {"step": step, "val_loss": val}),
-                      flush=True)
+                print("PDO_EVAL " + json.dumps({"step": step, **val} if resnet or ctr
+                                               else {"step": step, "val_loss": val}), flush=True)
         if step % args.log_every == 0 or step == args.steps:
             if dev.type == "cuda":
                 torch.cuda.synchronize(dev)
@@ -221,13 +240,13 @@ def run_collective(args, jenv) -> int:
             last = now
             if b.rank == 0:
                 log(f"step {step}/{args.steps} loss {float(loss.detach()):.4f} {rate:,.0f} "
-                    f"{'tokens' if args.workload == 'gpt2' else 'img'}/s (job)")
+                    f"{'tokens' if gpt2 else 'samples' if ctr else 'img'}/s (job)")
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     if gpt2:
         trainer.check_data()
-    if gpt2 or resnet:
+    if gpt2 or resnet or ctr:
         trainer.close()
     if args.ckpt_dir and b.rank == 0:
         ckpt.save(state(), args.ckpt_dir, step)

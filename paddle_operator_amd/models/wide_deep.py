@@ -49,6 +49,13 @@ class DeepTower(nn.Module):
         x = torch.cat([deep_emb.flatten(1), dense], dim=1)
         return self.mlp(x).squeeze(1) + wide_w.sum(dim=(1, 2)) + self.wide_bias
 
+    def logit_from_lookup(self, x, wide_sum, fm_term=None):
+        """The logit from ``ops.ctr_lookup``'s outputs: ``x [B, S·D + n_dense]`` (gathered
+        rows and dense features, already concatenated), ``wide_sum [B]`` and, for
+        DeepFM, the second-order term ``fm_term [B]``."""
+        out = self.mlp(x).squeeze(1) + wide_sum + self.wide_bias
+        return out if fm_term is None else out + fm_term
+
 
 class DeepFMTower(DeepTower):
     """DeepFM: the wide (first-order) term + a factorisation-machine

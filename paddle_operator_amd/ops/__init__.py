@@ -4,7 +4,8 @@
   ``linear``, the batched Wᵀ and deferred column sums;
 * ``ops.gpt2``   — LayerNorm, MLP, attention, LM head + cross-entropy, embedding;
 * ``ops.resnet`` — convolutions, BatchNorm, the stem;
-* ``ops.optim``  — the fused flat AdamW.
+* ``ops.optim``  — the fused flat AdamW;
+* ``ops.ctr``    — the CTR models' fused sparse lookup and sparse Adagrad step.
 
 Every op has a HIP path (GPU tensors; a missing extension raises) and a plain
 PyTorch fp32 reference (CPU, and the oracle of the numerics tests).
@@ -27,8 +28,11 @@ from .resnet import (  # noqa: F401
     _RES_MASK_USED, _STEM_POOL, _apply_bitmask, _stem_ok, bn_act, conv1x1, conv_bn_act, conv_bn_ds_act,
     conv_bn_relu_maxpool, global_avg_pool,
     max_pool_3x3s2)
+from .ctr import (  # noqa: F401
+    ctr_lookup, ctr_sparse_step, ref_ctr_lookup, ref_ctr_sparse_step, ref_run_sums)
 
 __all__ = [
+    "ctr_lookup", "ctr_sparse_step", "ref_ctr_lookup", "ref_ctr_sparse_step",
     "layer_norm", "layer_norm_res", "add_layer_norm", "bias_gelu", "attention", "cross_entropy",
     "embedding", "ref_layer_norm", "ref_bias_gelu", "ref_attention",
     "ref_cross_entropy", "use_hip", "linear", "mlp", "qkv_attention", "lm_head_xent",
