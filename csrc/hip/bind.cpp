@@ -1507,6 +1507,65 @@ py::object image_batch(std::optional<at::Tensor> img, std::optional<at::Tensor> 
   return py::make_tuple(x, y);
 }
 
+// One batch of click-log records (click.hip): cat = the raw categorical values [n, S] (an int32
+// tensor carrying the uint32 bits), dense int32 [n, n_dense], label uint8 [n], or with
+// staged = true the [B, …] buffers gathered on the host; stats fp32 [2, n_dense] (min, diff).
+// draw = (seed, stream, m, rank); V = vocab_per_slot.  Returns (ids int64 [B, S], dense fp32
+// [B, n_dense], label fp32 [B]).  rec_out (int64 [B]) receives the drawn records (−1 on pad
+// rows); cat = None writes only rec_out (returns None).
+py::object click_batch(std::optional<at::Tensor> cat, std::optional<at::Tensor> dense, std::optional<at::Tensor> label,
+                       std::optional<at::Tensor> stats, int64_t n, int64_t B, int64_t S, int64_t n_dense, int64_t V,
+                       std::tuple<uint64_t, int64_t, uint64_t, int64_t> draw, int64_t Bglobal, bool staged,
+                       std::optional<at::Tensor> rec_out) {
+  TORCH_CHECK(B >= 1 && S >= 1 && n_dense >= 1 && B <= INT_MAX && S <= INT_MAX && n_dense <= INT_MAX &&
+              B * S <= INT_MAX && B * n_dense <= INT_MAX,
+              "click_batch: B, S, n_dense >= 1 with B*S <= INT_MAX and B*n_dense <= INT_MAX required");
+  TORCH_CHECK(n >= 1 && n < (1LL << 31), "click_batch: 1 <= n < 2^31 records required");
+  TORCH_CHECK(V >= 1 && V <= (1LL << 31), "click_batch: 1 <= vocab_per_slot <= 2^31 required, got ", V);
+  const auto [seed, stream, m, rank] = draw;
+  TORCH_CHECK(stream == 0 || stream == 1, "click_batch: stream is 0 (training) or 1 (evaluation)");
+  TORCH_CHECK(rank >= 0 && (rank + 1) * B <= (1LL << 32), "click_batch: global row rank*B + j must stay below 2^32");
+  TORCH_CHECK(Bglobal >= B && Bglobal <= (1LL << 31), "click_batch: Bglobal = world*B, at most 2^31");
+  pdo::DataDraw d;
+  d.key0 = (uint32_t)seed;
+  d.key1 = (uint32_t)(seed >> 32);
+  d.stream = (uint32_t)stream;
+  d.step = (uint32_t)m;  // m mod 2^32
+  d.row0 = (uint64_t)rank * (uint64_t)B;
+  int64_t* rp = nullptr;
+  if (rec_out) {
+    CHECK_IN(*rec_out); CHECK_I64(*rec_out);
+    TORCH_CHECK(rec_out->numel() == B, "click_batch: rec_out must hold B values");
+    rp = rec_out->data_ptr<int64_t>();
+  }
+  if (!cat) {
+    TORCH_CHECK(rp != nullptr, "click_batch: cat = None needs rec_out");
+    CHECK_RC(pdo::click_batch(nullptr, nullptr, nullptr, nullptr, n, (int)B, (int)S, (int)n_dense, V, nullptr, nullptr,
+                              nullptr, d, Bglobal, false, rp, cur_stream()), "click_batch");
+    return py::none();
+  }
+  TORCH_CHECK(dense.has_value() && label.has_value() && stats.has_value(),
+              "click_batch: dense, label and stats required with cat");
+  CHECK_IN(*cat); CHECK_IN(*dense); CHECK_IN(*label); CHECK_IN(*stats); CHECK_F32(*stats);
+  TORCH_CHECK(cat->scalar_type() == at::kInt && dense->scalar_type() == at::kInt && label->scalar_type() == at::kByte,
+              "click_batch: cat must be int32 (the uint32 bits), dense int32 and label uint8");
+  const int64_t held = staged ? B : n;
+  TORCH_CHECK(cat->numel() == held * S && dense->numel() == held * n_dense && label->numel() == held,
+              "click_batch: cat, dense and label must hold ", held, " records of ", S, " slots and ", n_dense,
+              " dense features");
+  TORCH_CHECK(stats->numel() == 2 * n_dense, "click_batch: stats must be fp32 [2, n_dense]");
+  TORCH_CHECK(dense->device() == cat->device() && label->device() == cat->device() && stats->device() == cat->device() &&
+              (!rec_out || rec_out->device() == cat->device()), "click_batch: tensors on different devices");
+  auto ids = at::empty({B, S}, cat->options().dtype(at::kLong));
+  auto dn = at::empty({B, n_dense}, cat->options().dtype(at::kFloat));
+  auto lb = at::empty({B}, cat->options().dtype(at::kFloat));
+  CHECK_RC(pdo::click_batch(reinterpret_cast<const uint32_t*>(cat->data_ptr<int>()), dense->data_ptr<int>(),
+                            label->data_ptr<uint8_t>(), fp(*stats), n, (int)B, (int)S, (int)n_dense, V,
+                            ids.data_ptr<int64_t>(), fp(dn), fp(lb), d, Bglobal, staged, rp, cur_stream()),
+           "click_batch");
+  return py::make_tuple(ids, dn, lb);
+}
+
 // flat[off_i : off_i + n_i] = scale * t_i for every tensor (one launch);
 // reverse: t_i = flat[off_i : off_i + n_i].  bf16 or f32, all one dtype.
 void flatten_scale(std::vector<at::Tensor> ts, at::Tensor flat, std::vector<int64_t> offsets, double scale,
@@ -1757,6 +1816,9 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.def("image_batch", &image_batch, py::arg("img"), py::arg("lab"), py::arg("n"), py::arg("B"), py::arg("R"),
         py::arg("res"), py::arg("norm"), py::arg("draw"), py::arg("Bglobal"), py::arg("staged") = false,
         py::arg("x_out") = py::none(), py::arg("y_out") = py::none(), py::arg("boxes_out") = py::none());
+  m.def("click_batch", &click_batch, py::arg("cat"), py::arg("dense"), py::arg("label"), py::arg("stats"), py::arg("n"),
+        py::arg("B"), py::arg("S"), py::arg("n_dense"), py::arg("V"), py::arg("draw"), py::arg("Bglobal"),
+        py::arg("staged") = false, py::arg("rec_out") = py::none());
   m.def("flatten_scale", &flatten_scale);
   m.def("cast_scale_bf16_f32", &cast_scale_bf16_f32);
   m.def("cast_f32_bf16", &cast_f32_bf16);

@@ -341,4 +341,17 @@ struct ImageNorm {
 int image_batch(const uint8_t* img, const int* lab, long long n, int B, int R, int res, const ImageNorm& nm, bf16* x,
                 int64_t* y, const DataDraw& draw, long long Bglobal, bool staged, int* boxes_out, hipStream_t st);
 
+// click.hip: one batch of click-log records for the CTR trainer.  cat uint32 [n][S] (raw
+// categorical values), dense int32 [n][n_dense] (INT_MIN = missing), label uint8 [n], stats
+// fp32 [2][n_dense] (min, diff) → ids int64 [B][S] = s·V + ((fmix32(c ^ salt_s)·V) >> 32),
+// dense_out fp32 [B][n_dense] = (float(v) − min) / diff (+0.0 when missing), label_out fp32 [B].
+// The record of row j is drawn here (DataDraw; stream 1 = record m·Bglobal + g, and past n a
+// pad row: ids −1, dense +0.0, label −1).  staged: cat / dense / label are [B][…] buffers
+// gathered on the host and row j reads entry j.  1 ≤ n < 2³¹, 1 ≤ V ≤ 2³¹, B·S ≤ INT_MAX.
+// rec_out (optional): int64 [B], the drawn records (−1 on pad rows); cat == nullptr writes
+// only rec_out.
+int click_batch(const uint32_t* cat, const int* dense, const uint8_t* label, const float* stats, long long n, int B,
+                int S, int n_dense, long long V, int64_t* ids, float* dense_out, float* label_out, const DataDraw& draw,
+                long long Bglobal, bool staged, int64_t* rec_out, hipStream_t st);
+
 }  // namespace pdo

@@ -33,7 +33,10 @@ synchronises.
 
 The ResNet trainer's image directories follow the same conventions:
 :class:`ImageStream`, :func:`crop_boxes`, :func:`image_batch_ref` and ``IMAGE_DOC``
-in the second half of this module (kernel ``csrc/hip/image.hip``).
+in the second part of this module (kernel ``csrc/hip/image.hip``), and so do the CTR
+trainer's click directories: :class:`ClickStream`, :func:`record_index`, :func:`hash_rows`,
+:func:`dense_norm`, :func:`click_batch_ref` and ``CLICK_DOC`` in the third part (kernel
+``csrc/hip/click.hip``).
 """
 from __future__ import annotations
 
@@ -499,6 +502,291 @@ class ImageStream:
             xb.copy_(x)
             x = xb
         return x, y
+
+    def close(self):
+        if self._pool is not None:
+            if self._next is not None:
+                self._next[1].result()
+            self._pool.shutdown(wait=True)
+            self._pool = None
+            self._next = None
+
+
+# ----------------------------------------------------------------------------------------------
+# Click logs and the replayable record sampler of the CTR trainer (Wide&Deep, DeepFM)
+# ----------------------------------------------------------------------------------------------
+CLICK_DOC = """
+**File format.**  A directory of four arrays opened with ``np.load(mmap_mode="r")``, all in C
+order, ``1 ≤ n < 2³¹`` records: ``cat.npy`` (uint32 ``[n, S]``, the raw categorical value of
+each slot — Criteo's 8-hex-digit tokens are exactly 32 bits; ``0`` is the value written for a
+missing field and is hashed like any other), ``dense.npy`` (int32 ``[n, n_dense]``, the raw
+integer features, ``−2³¹`` = missing), ``label.npy`` (uint8 ``[n]``, 0 or 1) and
+``dense_stats.npy`` (float32 ``[2, n_dense]``: row 0 ``min``, row 1 ``diff``; all finite,
+``diff > 0``).  ``S`` and ``n_dense`` are the model's ``n_sparse`` / ``n_dense``.
+
+**Draw.**  The image sampler's convention: row ``j`` of rank ``rank`` is global row
+``g = rank·B + j`` (``g < 2³²``), key = (low, high) words of the 64-bit seed.  Training
+(stream 0): one Philox4x32-10 call with counter ``(g, 0, stream, m mod 2³²)``,
+``i = ((w1 << 32) | w0) mod n`` — sampling with replacement.  Evaluation (stream 1) is not
+random: ``i = (m mod 2³²)·Bglobal + g`` (``Bglobal = world·B``); a row with ``i ≥ n`` is a pad
+row — every id ``−1``, every dense value ``+0.0``, label ``−1`` — so ``ceil(n / Bglobal)``
+batches visit every record exactly once for any ``world × B``.  :func:`record_index` is the
+host reference of the draw (``−1`` on a pad row).
+
+**Hash.**  Slot ``s``, raw value ``c``, ``V = vocab_per_slot ∈ [1, 2³¹]``:
+``salt_s = ((s + 1)·0x9E3779B9) mod 2³²``; ``h = fmix32(c ^ salt_s)``, murmur3's finaliser
+(``h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16``, all mod 2³²);
+``ids[j, s] = s·V + ((h·V) >> 32)`` in 64-bit arithmetic.  ``fmix32`` is a bijection, so distinct
+values of one slot collide only through the reduction to ``V``.  :func:`hash_rows`.
+
+**Dense.**  ``dense[j, k] = +0.0`` if the stored value is ``−2³¹``, otherwise
+``fl(fl(float(v) − min[k]) / diff[k])``: ``float(v)`` is the round-to-nearest-even int → fp32
+conversion and the division the correctly rounded IEEE one — the min–max rule of Paddle's
+Criteo readers, exact in numpy float32.  :func:`dense_norm`.
+
+**Label.**  ``float(label[i])``.
+
+**Outputs.**  ``ids`` int64 ``[B, S]``, ``dense`` fp32 ``[B, n_dense]``, ``label`` fp32 ``[B]``:
+what ``ops.ctr_lookup`` and the loss take.  ``ctr_lookup`` reads zeros for id ``−1`` and the
+sparse step ignores it.  :func:`click_batch_ref` is the host reference of the kernel
+(``csrc/hip/click.hip``) and the CPU trainer's path.
+
+**Placement.**  As for tokens and images: device-resident when ``n·(4S + 4n_dense + 1)`` bytes
+fit ``device_gb`` (one launch draws, hashes, normalises and stores); otherwise a worker gathers
+the next batch's ``B`` records into one of two pinned buffer sets and copies them one batch ahead
+on a side stream, and the same kernel — still drawing the record, so that it knows the pad
+rows — reads the staged buffers.  Both routes write identical tensors.
+"""
+
+_I32_MIN = -(1 << 31)
+
+
+def record_index(seed: int, stream: int, m: int, rank: int, B: int, n: int, Bglobal: int | None = None) -> np.ndarray:
+    """The records of batch ``m`` for rows ``rank·B … rank·B + B − 1``: ``int64[B]``, ``−1`` past
+    the end of the evaluation set (``CLICK_DOC``)."""
+    if not (1 <= n < 1 << 31 and B >= 1):
+        raise ValueError(f"record_index: need 1 <= n < 2^31 and B >= 1, got n={n}, B={B}")
+    if rank < 0 or (rank + 1) * B > 1 << 32:
+        raise ValueError(f"record_index: global rows rank*B + j must stay below 2^32 (rank={rank}, B={B})")
+    g = np.arange(rank * B, (rank + 1) * B, dtype=np.uint64)
+    m32 = int(m) & _U32
+    if stream != TRAIN_STREAM:
+        base = m32 * (B if Bglobal is None else int(Bglobal))  # a Python int: up to 2^63
+        if base >= n:
+            return np.full(B, -1, dtype=np.int64)
+        i = base + g.astype(np.int64)
+        return np.where(i < n, i, -1)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w0, w1, _, _ = philox4x32_10((g, 0, int(stream), m32), (seed & _U32, seed >> 32))
+    return (((w1 << np.uint64(32)) | w0) % np.uint64(n)).astype(np.int64)
+
+
+def hash_rows(cat: np.ndarray, V: int) -> np.ndarray:
+    """Table rows of the raw values ``cat`` (uint32 ``[..., S]``, slot = last axis): int64 of the
+    same shape, ``s·V + ((fmix32(c ^ salt_s)·V) >> 32)`` (``CLICK_DOC``)."""
+    if not 1 <= V <= 1 << 31:
+        raise ValueError(f"hash_rows: vocab_per_slot must be in [1, 2^31], got {V}")
+    u, mask = np.uint64, np.uint64(_U32)
+    s = np.arange(cat.shape[-1], dtype=np.uint64)
+    h = (np.asarray(cat).astype(np.uint64) ^ (((s + u(1)) * u(0x9E3779B9)) & mask))
+    h ^= h >> u(16)
+    h = (h * u(0x85EBCA6B)) & mask
+    h ^= h >> u(13)
+    h = (h * u(0xC2B2AE35)) & mask
+    h ^= h >> u(16)
+    return (s * u(V) + ((h * u(V)) >> u(32))).astype(np.int64)
+
+
+def dense_norm(raw: np.ndarray, stats: np.ndarray) -> np.ndarray:
+    """``(float(v) − min) / diff`` in float32, ``+0.0`` where the stored value is ``−2³¹``
+    (``raw`` int32 ``[..., n_dense]``, ``stats`` float32 ``[2, n_dense]``; ``CLICK_DOC``)."""
+    raw = np.asarray(raw, dtype=np.int32)
+    stats = np.asarray(stats, dtype=np.float32)
+    x = (raw.astype(np.float32) - stats[0]) / stats[1]  # each operation rounds once, to nearest even
+    return np.where(raw == _I32_MIN, np.float32(0.0), x).astype(np.float32)
+
+
+def click_batch_ref(cat, dense, label, stats, rec: np.ndarray, V: int, staged: bool = False):
+    """Host reference of ``click_batch``: ``(ids, dense, label)`` = int64 ``[B, S]``, fp32
+    ``[B, n_dense]`` and fp32 ``[B]`` torch tensors for the drawn records ``rec``
+    (:func:`record_index`).  ``staged``: row ``j`` reads entry ``j`` of the arrays."""
+    rec = np.asarray(rec, dtype=np.int64)
+    B, live = rec.shape[0], rec >= 0
+    src = np.flatnonzero(live) if staged else rec[live]
+    ids = np.full((B, cat.shape[1]), -1, dtype=np.int64)
+    x = np.zeros((B, dense.shape[1]), dtype=np.float32)
+    y = np.full(B, -1.0, dtype=np.float32)
+    if src.size:
+        ids[live] = hash_rows(np.asarray(cat)[src], V)
+        x[live] = dense_norm(np.asarray(dense)[src], stats)
+        y[live] = np.asarray(label)[src].astype(np.float32)
+    return torch.from_numpy(ids), torch.from_numpy(x), torch.from_numpy(y)
+
+
+def open_clicks(path: str, S: int, n_dense: int):
+    """``(cat, dense, label, stats)`` of the click directory ``path`` after the format checks
+    (the first three are memmaps, ``stats`` a float32 array)."""
+    fc, fd, fl, fs = (os.path.join(path, f) for f in ("cat.npy", "dense.npy", "label.npy", "dense_stats.npy"))
+    cat, dense, label = (np.load(f, mmap_mode="r") for f in (fc, fd, fl))
+    stats = np.load(fs, mmap_mode="r")
+    for f, a, dt in ((fc, cat, np.uint32), (fd, dense, np.int32), (fl, label, np.uint8), (fs, stats, np.float32)):
+        if a.dtype != dt:
+            raise ValueError(f"{f}: dtype {a.dtype}, must be {np.dtype(dt)}")
+        if not a.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"{f}: must be stored in C order")
+    if cat.ndim != 2 or cat.shape[1] != S:
+        raise ValueError(f"{fc}: shape {cat.shape}, the model has {S} sparse slots: [n, {S}] expected")
+    n = cat.shape[0]
+    if not 1 <= n < 1 << 31:
+        raise ValueError(f"{fc}: {n} records, 1 <= n < 2^31 required")
+    if dense.ndim != 2 or dense.shape[1] != n_dense:
+        raise ValueError(f"{fd}: shape {dense.shape}, the model has {n_dense} dense features: [n, {n_dense}] expected")
+    if dense.shape[0] != n:
+        raise ValueError(f"{fd}: {dense.shape[0]} records, {fc} has {n}")
+    if label.ndim != 1 or label.shape[0] != n:
+        raise ValueError(f"{fl}: shape {label.shape}, {fc} has {n} records: [{n}] expected")
+    if int(label.max()) > 1:
+        raise ValueError(f"{fl}: labels must be 0 or 1, found {int(label.max())}")
+    return cat, dense, label, check_click_stats(stats, n_dense, fs)
+
+
+def check_click_stats(stats, n_dense: int, name: str) -> np.ndarray:
+    """``stats`` as a float32 ``[2, n_dense]`` array (min, diff) after its checks."""
+    stats = np.array(stats)
+    if stats.dtype != np.float32 or stats.shape != (2, n_dense):
+        raise ValueError(f"{name}: dtype {stats.dtype} shape {stats.shape}, must be float32 [2, {n_dense}]")
+    if not np.isfinite(stats).all() or not (stats[1] > 0).all():
+        raise ValueError(f"{name}: min and diff must be finite and diff > 0")
+    return stats
+
+
+class ClickStream:
+    """Batches of one click directory on one rank: ``batch(m) -> (ids, dense, label)``, int64
+    ``[B, S]``, fp32 ``[B, n_dense]`` and fp32 ``[B]`` on ``device``.  ``stats`` (float32
+    ``[2, n_dense]``) replaces the directory's own ``dense_stats.npy``: a validation stream is
+    normalised with the training set's.
+    """
+    __doc__ += CLICK_DOC
+
+    def __init__(self, path: str, B: int, S: int, n_dense: int, vocab_per_slot: int, device, seed: int = 0,
+                 stream: int = TRAIN_STREAM, rank: int = 0, world: int = 1, device_gb: float = 8.0, stats=None):
+        self.path, self.B, self.S, self.n_dense, self.V = str(path), int(B), int(S), int(n_dense), int(vocab_per_slot)
+        self.device = torch.device(device)
+        self.seed, self.stream, self.rank = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(rank)
+        self.Bglobal = int(world) * self.B
+        if rank < 0 or rank >= world or self.Bglobal > 1 << 31:
+            raise ValueError(f"need 0 <= rank < world and world*B <= 2^31 (rank={rank}, world={world}, B={B})")
+        if not 1 <= self.V <= 1 << 31:
+            raise ValueError(f"vocab_per_slot must be in [1, 2^31], got {vocab_per_slot}")
+        if self.B * self.S >= 1 << 31:
+            raise ValueError(f"B*S must stay below 2^31 (B={B}, S={S})")
+        self.cat, self.dense, self.label, own = open_clicks(self.path, self.S, self.n_dense)
+        self.stats = own if stats is None else check_click_stats(stats, self.n_dense, "stats")
+        self.n = int(self.cat.shape[0])
+        self.set = None
+        self._pool = None
+        if self.device.type == "cuda":
+            self._hip = _native.require_hip()
+            self._stats_dev = torch.from_numpy(self.stats).to(self.device)
+            if self.n * (4 * self.S + 4 * self.n_dense + 1) <= device_gb * 2**30:
+                # uploaded in pieces of about 256 MiB, so the host never holds a second copy of the files;
+                # int32 carries cat's bits (the kernel reads them as uint32)
+                dev = self.device
+                self.set = (torch.empty((self.n, self.S), dtype=torch.int32, device=dev),
+                            torch.empty((self.n, self.n_dense), dtype=torch.int32, device=dev),
+                            torch.empty(self.n, dtype=torch.uint8, device=dev))
+                per = max(1, (256 << 20) // (4 * max(self.S, self.n_dense)))
+                for o in range(0, self.n, per):
+                    self.set[0][o:o + per].copy_(torch.from_numpy(np.array(self.cat[o:o + per]).view(np.int32)))
+                    self.set[1][o:o + per].copy_(torch.from_numpy(np.array(self.dense[o:o + per])))
+                    self.set[2][o:o + per].copy_(torch.from_numpy(np.array(self.label[o:o + per])))
+            else:
+                self._init_staging()
+        self.placement = "cpu" if self.device.type != "cuda" else ("device" if self.set is not None else "host")
+
+    def batches_per_epoch(self) -> int:
+        """Batches of the evaluation stream that cover the set once: ``ceil(n / (world·B))``."""
+        return -(-self.n // self.Bglobal)
+
+    # -- host side ----------------------------------------------------------
+    def records(self, m: int) -> np.ndarray:
+        return record_index(self.seed, self.stream, m, self.rank, self.B, self.n, self.Bglobal)
+
+    def host_batch(self, m: int):
+        """``(ids, dense, label)`` of batch ``m`` built with numpy: the reference of both GPU
+        routes and the CPU trainer's path."""
+        return click_batch_ref(self.cat, self.dense, self.label, self.stats, self.records(m), self.V)
+
+    def _gather(self, m: int, outs):
+        """The records of batch ``m`` into the ``[B, …]`` buffers ``outs`` = (cat, dense, label); a pad
+        row's entry is left as it is."""
+        rec = self.records(m)
+        live = rec >= 0
+        for a, o in zip((self.cat, self.dense, self.label), outs):
+            if live.all():
+                np.take(a, rec, axis=0, out=o, mode="clip")  # rec < n: nothing is clipped, no bounce buffer
+            elif live.any():
+                o[live] = a[rec[live]]
+
+    # -- host-staged route --------------------------------------------------
+    def _init_staging(self):
+        import concurrent.futures as cf
+        shapes = (((self.B, self.S), torch.int32), ((self.B, self.n_dense), torch.int32), ((self.B,), torch.uint8))
+        self._pinned = [[torch.zeros(s, dtype=d).pin_memory() for s, d in shapes] for _ in range(2)]
+        self._staged = [[torch.zeros(s, dtype=d, device=self.device) for s, d in shapes] for _ in range(2)]
+        self._consumed = [None, None]  # compute-stream events: the kernel has read staged[k]
+        self._side = torch.cuda.Stream(self.device)
+        self._pool = cf.ThreadPoolExecutor(max_workers=1, thread_name_prefix="pdo-data")
+        self._next = None  # (m, future) of the batch on its way
+        self._slot = 0
+
+    def _stage(self, m: int, k: int, consumed):
+        """Worker thread: gather batch ``m`` into the pinned buffers ``k`` and copy them to the
+        staged buffers ``k`` on the side stream (the event discipline of ``ImageStream._stage``)."""
+        pc, pd, pl = self._pinned[k]
+        self._gather(m, (pc.numpy().view(np.uint32), pd.numpy(), pl.numpy()))
+        with torch.cuda.stream(self._side):
+            if consumed is not None:
+                self._side.wait_event(consumed)
+            for dst, src in zip(self._staged[k], self._pinned[k]):
+                dst.copy_(src, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._side)
+        ev.synchronize()  # this thread only: the pinned buffers may be rewritten two batches on
+        return k, ev
+
+    def _submit(self, m: int):
+        k = self._slot
+        self._slot ^= 1
+        self._next = (m, self._pool.submit(self._stage, m, k, self._consumed[k]))
+
+    def _staged_batch(self, m: int):
+        if self._next is None or self._next[0] != m:
+            if self._next is not None:
+                self._next[1].result()  # a jump in m (resume, evaluation restart): drop what was on its way
+            self._submit(m)
+        k, ev = self._next[1].result()
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ev)
+        out = self._launch(self._staged[k], m, True)
+        done = torch.cuda.Event()
+        done.record(cur)
+        self._consumed[k] = done
+        self._submit(m + 1)
+        return out
+
+    def _launch(self, arrays, m, staged):
+        cat, dense, label = arrays
+        return self._hip.click_batch(cat, dense, label, self._stats_dev, self.n, self.B, self.S, self.n_dense, self.V,
+                                     (self.seed, self.stream, int(m) & _U32, self.rank), self.Bglobal, staged)
+
+    # -- API ------------------------------------------------------------------
+    def batch(self, m: int):
+        if self.set is not None:
+            return self._launch(self.set, m, False)
+        if self._pool is not None:
+            return self._staged_batch(m)
+        return tuple(t.to(self.device) for t in self.host_batch(m))
 
     def close(self):
         if self._pool is not None:

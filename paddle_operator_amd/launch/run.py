@@ -50,16 +50,21 @@ def parse_args(argv=None):
     ap.add_argument("--dropout-seed", type=int, default=0, help="gpt2: seed of the dropout masks")
     ap.add_argument("--data", default=os.environ.get("PDO_TRAIN_DATA", ""),
                     help="gpt2: training token file, raw little-endian uint16 ids (nanoGPT train.bin); resnet50: "
-                         "directory with images.npy (uint8 [n, R, R, 3]) and labels.npy ([n]); default: synthetic "
-                         "batches")
+                         "directory with images.npy (uint8 [n, R, R, 3]) and labels.npy ([n]); wide_deep / deepfm "
+                         "without pservers: click directory with cat.npy (uint32 [n, 26]), dense.npy (int32 "
+                         "[n, 13]), label.npy (uint8 [n]) and dense_stats.npy (tools/criteo_to_clicks.py); default: "
+                         "synthetic batches")
     ap.add_argument("--val-data", default=os.environ.get("PDO_VAL_DATA", ""),
-                    help="gpt2 / resnet50: held-out token file / image directory of the same format (--eval-every)")
+                    help="held-out token file / image directory / click directory of the same format (--eval-every)")
     ap.add_argument("--data-seed", type=int, default=0,
-                    help="gpt2 / resnet50: 64-bit seed of the window / crop sampler; wide_deep / deepfm: seed of "
-                         "the synthetic batches")
+                    help="64-bit seed of the window / crop / record sampler; wide_deep / deepfm without --data: "
+                         "seed of the synthetic batches")
     ap.add_argument("--data-device-gb", type=float, default=8.0,
-                    help="gpt2 / resnet50: a token file / image set up to this size is held in GPU memory; a larger "
+                    help="a token file / image set / click set up to this size is held in GPU memory; a larger "
                          "one is read from the host one micro-batch ahead")
+    ap.add_argument("--vocab-per-slot", type=int, default=None,
+                    help="wide_deep / deepfm without pservers: table rows per sparse slot, into which --data's raw "
+                         "categorical values are hashed (default 10000; 1000 with --tiny)")
     ap.add_argument("--grad-accum", type=int, default=None,
                     help="gpt2: micro-batches per optimizer step (default 1); --steps counts optimizer steps")
     ap.add_argument("--lr", type=float, default=None,
@@ -78,10 +83,11 @@ def parse_args(argv=None):
     ap.add_argument("--eval-every", type=int, default=0,
                     help="gpt2: held-out loss, resnet50: held-out loss / top-1 / top-5, on --val-data every N "
                          "optimizer steps (PDO_EVAL records); wide_deep / deepfm without pservers: held-out "
-                         "log-loss and AUC on a synthetic validation stream, no --val-data needed")
+                         "log-loss and AUC, on --val-data when --data is given, else on a synthetic validation "
+                         "stream that needs no --val-data")
     ap.add_argument("--eval-batches", type=int, default=None,
-                    help="micro-batches per rank of one evaluation (gpt2: default 8; resnet50: default 0 = the "
-                         "whole set once)")
+                    help="micro-batches per rank of one evaluation (gpt2: default 8; resnet50, and wide_deep / "
+                         "deepfm with --val-data: default 0 = the whole set once)")
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="resnet50: keep the step eager (default on one GPU rank: captured once into a HIP graph "
                          "and replayed, workloads/resnet.py; multi-rank steps stay eager)")
@@ -104,11 +110,19 @@ def parse_args(argv=None):
     ctr = args.workload in ("wide_deep", "deepfm")
     if args.eval_every and not args.val_data and not ctr:
         ap.error("--eval-every needs --val-data (or PDO_VAL_DATA)")
+    if ctr and args.eval_every and args.data and not args.val_data:
+        ap.error("--eval-every with --data needs --val-data (or PDO_VAL_DATA): a model trained on a click "
+                 "directory is not scored on the synthetic stream")
+    if ctr and (args.data or args.val_data) and os.environ.get("PADDLE_PSERVERS_IP_PORT_LIST", "").strip():
+        ap.error("--data / --val-data: click directories feed the GPU trainer; a parameter-server job "
+                 "(PADDLE_PSERVERS_IP_PORT_LIST is set) trains on synthetic batches")
+    if args.vocab_per_slot is not None and (not ctr or args.vocab_per_slot < 1):
+        ap.error("--vocab-per-slot is a positive row count of the wide_deep / deepfm tables")
     args.lr_given = args.lr is not None  # the records carry only flags that were given
     if args.lr is None:
         args.lr = 0.1 if args.workload == "resnet50" else 1e-3 if ctr else 3e-4
     if args.eval_batches is None:
-        args.eval_batches = 0 if args.workload == "resnet50" else 8
+        args.eval_batches = 0 if args.workload == "resnet50" or ctr and args.val_data else 8
     return args
 
 
@@ -168,8 +182,11 @@ def run_collective(args, jenv) -> int:
         from ..workloads.ctr import CTRTrainer
         cfg = (WideDeepConfig(vocab_per_slot=1000, model=args.workload) if args.tiny
                else WideDeepConfig(model=args.workload))
+        if args.vocab_per_slot is not None:
+            cfg.vocab_per_slot = args.vocab_per_slot
         trainer = CTRTrainer(cfg, args.batch or (64 if args.tiny else 4096), dev, lr=args.lr,
-                             sparse_lr=args.sparse_lr, data_seed=args.data_seed)
+                             sparse_lr=args.sparse_lr, data_seed=args.data_seed, data=args.data or None,
+                             val_data=args.val_data or None, data_device_gb=args.data_device_gb)
         trainer.sync_initial_weights()
         tokens_per_step = trainer.B  # samples
     start_step = 0
@@ -259,6 +276,8 @@ def run_collective(args, jenv) -> int:
         summary.update(_gpt2_flags(args))
     if resnet:
         summary.update(_resnet_flags(args))
+    if ctr:
+        summary.update(_ctr_flags(args))
     if val_loss is not None:
         summary["val_loss"] = val_loss
     print("PDO_DONE " + json.dumps(summary), flush=True)
@@ -291,6 +310,19 @@ def _resnet_flags(args) -> dict:
         out["lr"] = args.lr
     if args.lr_schedule is not None:
         out["lr_schedule"] = args.lr_schedule
+    return out
+
+
+def _ctr_flags(args) -> dict:
+    """The click-data flags that were given to a wide_deep / deepfm run, for its PDO_DONE and
+    PDO_BENCH records (absent keys: the flag was not given)."""
+    out = {}
+    if args.data:
+        out["data"] = args.data
+    if args.val_data:
+        out["val_data"] = args.val_data
+    if args.vocab_per_slot is not None:
+        out["vocab_per_slot"] = args.vocab_per_slot
     return out
 
 
@@ -340,6 +372,8 @@ def _bench(args, b, jenv, trainer, tokens_per_step, ready_rec) -> int:
         res.update(_gpt2_flags(args))
     if args.workload == "resnet50":
         res.update(_resnet_flags(args))
+    if args.workload in ("wide_deep", "deepfm"):
+        res.update(_ctr_flags(args))
     if dev.type == "cuda":
         res["gpu_name"] = torch.cuda.get_device_name(dev)
         res["max_mem_gb"] = round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)

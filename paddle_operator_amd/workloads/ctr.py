@@ -7,9 +7,13 @@ and applies row-wise Adagrad to the rows the batch touched — runs on
 torch reference on CPU tensors and under ``PDO_OPS=torch``).  The dense tower stays
 on torch in fp32 with Adam, as in ``parallel.ps.ShardServer``.
 
-Batches are synthetic and drawn on the device from a generator reseeded for every
-step from ``(data_seed, step counter, rank)`` alone, with the label rule of
-``models.wide_deep.synthetic_batch``; the step counter is in the checkpoint, so a
+Without ``data`` the batches are synthetic and drawn on the device from a generator
+reseeded for every step from ``(data_seed, step counter, rank)`` alone, with the label
+rule of ``models.wide_deep.synthetic_batch``.  With ``data`` / ``val_data`` they come from
+click directories (``data.ClickStream``, ``data.CLICK_DOC``): one launch of
+``csrc/hip/click.hip`` draws the batch's records, hashes the raw categorical values into
+table rows and normalises the dense features.  Either way a batch is a function of
+``(data_seed, step counter, rank)``, and the step counter is in the checkpoint, so a
 resumed job replays the batches the uninterrupted one would have seen.
 
 More than one rank: the tables are replicas.  A step all-gathers ``ids``, ``dX``,
@@ -54,7 +58,8 @@ def auc_from_scores(scores: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
 
 class CTRTrainer:
     def __init__(self, cfg: WideDeepConfig, batch: int, device, lr: float = 1e-3, sparse_lr: float = 0.05,
-                 data_seed: int = 0, eval_seed: int | None = None, seed: int = 0):
+                 data_seed: int = 0, eval_seed: int | None = None, seed: int = 0, data: str | None = None,
+                 val_data: str | None = None, data_device_gb: float = 8.0):
         self.cfg = cfg
         self.device = torch.device(device)
         self.B = int(batch)
@@ -80,11 +85,29 @@ class CTRTrainer:
         self.K = ctr_ops.min_ldx(cfg.n_sparse, cfg.emb_dim, cfg.n_dense)
         # rows of X and dX on 16 B for the kernels' vector accesses; the torch path needs no padding
         self.ldx = ctr_ops.padded_ldx(cfg.n_sparse, cfg.emb_dim, cfg.n_dense) if ctr_ops.use_hip(self.deep) else self.K
+        # click directories (data.ClickStream); the validation set is normalised with the training set's stats
+        self.train = self.val = None
+        if data or val_data:
+            from ..data import ClickStream
+            common = dict(seed=self.data_seed, rank=self.rank, world=self.world, device_gb=data_device_gb)
+            shape = (self.B, cfg.n_sparse, cfg.n_dense, cfg.vocab_per_slot, dev)
+            if data:
+                self.train = ClickStream(data, *shape, stream=TRAIN_STREAM, **common)
+            if val_data:
+                self.val = ClickStream(val_data, *shape, stream=EVAL_STREAM,
+                                       stats=self.train.stats if self.train is not None else None, **common)
 
     # ------------------------------------------------------------------ data
     def draw(self, stream: int, step: int, rank: int | None = None):
         """Batch ``step`` of a stream: ``(ids [B, S], dense [B, n_dense], label [B])`` on the
-        device, a function of ``(seed, stream, step, rank)`` only."""
+        device, a function of ``(seed, stream, step, rank)`` only.  With ``data`` / ``val_data``
+        the stream's batches come from the click directory (this rank's rows; on the validation
+        stream a row past the end of the set has ids −1 and label −1)."""
+        files = self.train if stream == TRAIN_STREAM else self.val
+        if files is not None:
+            if rank is not None and rank != self.rank:
+                raise ValueError(f"draw: a click stream serves its own rank {self.rank}, not {rank}")
+            return files.batch(step)
         cfg = self.cfg
         seed = self.data_seed if stream == TRAIN_STREAM else self.eval_seed
         self.gen.manual_seed(batch_seed(seed, stream, step, self.rank if rank is None else rank))
@@ -164,7 +187,14 @@ class CTRTrainer:
         """Held-out log-loss and AUC over batches 0 … n_batches − 1 of the validation stream
         (its own seed), summed over ranks by one all-reduce.  AUC is the rank statistic of
         one device sort per rank; over several ranks it is the pair-weighted mean of the
-        ranks' AUCs (positives and negatives are paired within a rank's share)."""
+        ranks' AUCs (positives and negatives are paired within a rank's share).
+
+        With ``val_data``: batches 0 … n_batches − 1 of the click directory's evaluation stream
+        (0: the whole set once, ``batches_per_epoch()``).  The ranks' logits and labels are
+        all-gathered, the pad rows (label −1) dropped, and loss and AUC computed over what is
+        left: the exact rank statistic of the whole set.  The result gains ``"records"``."""
+        if self.val is not None:
+            return self._evaluate_files(int(n_batches))
         nb = max(1, int(n_batches))
         logits, labels = [], []
         for m in range(nb):
@@ -186,8 +216,26 @@ class CTRTrainer:
         loss, cnt, u, pairs = tot.tolist()
         return {"val_loss": loss / max(cnt, 1.0), "auc": u / pairs if pairs > 0 else 0.5}
 
+    def _evaluate_files(self, n_batches: int) -> dict:
+        nb = n_batches if n_batches > 0 else self.val.batches_per_epoch()
+        logits, labels = [], []
+        for m in range(nb):
+            ids, dense, label = self.draw(EVAL_STREAM, m)
+            X, ws, fmt, _ = ctr_ops.ctr_lookup(ids, dense, self.deep, self.wide, self.fm, self.ldx)
+            logits.append(self.tower.logit_from_lookup(X[:, :self.K], ws, fmt))
+            labels.append(label)
+        z, y = self._gather(torch.cat(logits)), self._gather(torch.cat(labels))
+        keep = y >= 0
+        z, y = z[keep], y[keep]
+        loss = float(F.binary_cross_entropy_with_logits(z, y, reduction="sum").double())
+        u, pairs = auc_from_scores(z, y).tolist()
+        cnt = int(y.numel())
+        return {"val_loss": loss / max(cnt, 1), "auc": u / pairs if pairs > 0 else 0.5, "records": cnt}
+
     def close(self):
-        pass
+        for s in (self.train, self.val):
+            if s is not None:
+                s.close()
 
     # ------------------------------------------------------------------ checkpoint
     def state_dict(self):

@@ -2,13 +2,18 @@
 framework path (``PDO_OPS=torch``), interleaved in one process.
 
     python tools/bench_ctr.py [--models wide_deep,deepfm] [--batches 4096,32768]
-                              [--rounds 3] [--steps 20] [--warmup 5] [--out FILE]
+                              [--rounds 3] [--steps 20] [--warmup 5] [--out FILE] [--data DIR]
 
 Per model and batch: two ``CTRTrainer``s (same seeds, same batches), one built and
 stepped with ``PDO_OPS=hip``, one with ``PDO_OPS=torch``; each round times ``--steps``
 steps of one, then of the other (device events around the loop).  Then ``ctr_fwd``
 and ``ctr_bwd_rows`` alone (device events, 50 launches each, the sort outside), with
 the bytes each moves.  One JSON line per (model, batch).
+
+``--data DIR`` (a click directory, ``paddle_operator_amd.data.CLICK_DOC``) adds a third
+arm to the same rounds: the HIP step fed from the directory, device-resident
+(``files_device``) and host-staged (``files_host``); the synthetic ``hip`` arm is their
+yardstick.  Then ``click_batch`` alone, with its bytes, next to the synthetic draw.
 """
 import argparse
 import json
@@ -55,8 +60,20 @@ def kernels_alone(torch, tr, launches=50):
             "sort_us": round(us_sort, 1), "lookups": N, "rows_touched": uniq}
 
 
+def click_batch_alone(torch, tr, launches=50):
+    """µs and bytes of ``click_batch`` on the trainer's device-resident click set: per row it reads
+    S uint32, n_dense int32 and a label byte and writes S int64, n_dense fp32 and an fp32 label."""
+    s = tr.train
+    us = timed(torch, lambda: s.batch(3), launches) * 1e3
+    nbytes = s.B * (s.S * (4 + 8) + s.n_dense * (4 + 4) + 1 + 4)
+    return {"click_batch_us": round(us, 1), "click_batch_bytes": nbytes, "click_batch_GBps": round(nbytes / us / 1e3, 1)}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--data", default="",
+                    help="click directory (tools/criteo_to_clicks.py): adds the file-fed HIP step, device-resident "
+                         "(files_device) and host-staged (files_host), to the interleaved rounds")
     ap.add_argument("--models", default="wide_deep,deepfm")
     ap.add_argument("--batches", default="4096,32768")
     ap.add_argument("--rounds", type=int, default=3)
@@ -71,16 +88,21 @@ def main():
     for model in a.models.split(","):
         for batch in (int(b) for b in a.batches.split(",")):
             trainers = {}
-            for mode in ("hip", "torch"):
-                os.environ["PDO_OPS"] = mode
-                trainers[mode] = CTRTrainer(WideDeepConfig(model=model), batch, "cuda:0")
+            # with --data: the HIP step fed from the click directory, device-resident and host-staged
+            arms = {"hip": {}, "torch": {}}
+            if a.data:
+                arms["files_device"] = {"data": a.data, "data_device_gb": 1e6}
+                arms["files_host"] = {"data": a.data, "data_device_gb": 0.0}
+            for mode, kw in arms.items():
+                os.environ["PDO_OPS"] = "torch" if mode == "torch" else "hip"
+                trainers[mode] = CTRTrainer(WideDeepConfig(model=model), batch, "cuda:0", **kw)
                 for _ in range(a.warmup):
                     trainers[mode].step()
             torch.cuda.synchronize()
-            ms = {"hip": [], "torch": []}
+            ms = {mode: [] for mode in arms}
             for _ in range(a.rounds):
-                for mode in ("hip", "torch"):
-                    os.environ["PDO_OPS"] = mode
+                for mode in arms:
+                    os.environ["PDO_OPS"] = "torch" if mode == "torch" else "hip"
                     ms[mode].append(round(timed(torch, trainers[mode].step, a.steps), 3))
             loss = {}
             for mode in ("torch", "hip"):  # the same step count on both: the losses are comparable
@@ -90,8 +112,14 @@ def main():
                    "step_ms": ms, "samples_per_s": {m: [round(batch / t * 1e3) for t in v] for m, v in ms.items()},
                    "hip_faster_every_round": all(h < t for h, t in zip(ms["hip"], ms["torch"])), "loss": loss}
             rec.update(kernels_alone(torch, trainers["hip"]))
+            if a.data:
+                rec.update(click_batch_alone(torch, trainers["files_device"]))
+                rec["synthetic_draw_us"] = round(timed(torch, lambda: trainers["hip"].draw(0, 3), 50) * 1e3, 1)
+                rec["click_records"] = trainers["files_device"].train.n
             lines.append(json.dumps(rec))
             print(lines[-1], flush=True)
+            for t in trainers.values():
+                t.close()
             del trainers
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
