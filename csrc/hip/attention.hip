@@ -21,8 +21,8 @@
 //     first and also writes delta = rowsum(dO ∘ O) (its dO fragments are
 //     already in registers) and lse·log2e, which dK/dV then DMAs: no
 //     separate delta pass.
-// Staging choice per kernel measured in the training step (profiled with tools/gpu.sh step / soab:
-// rocprofv3 per-kernel times of extension variants in one session): LDS-DMA
+// Staging choice per kernel measured in the training step (rocprofv3
+// per-kernel times of extension variants in one session): LDS-DMA
 // wins for dK/dV (427.7 vs 448.0 µs) but not for the forward (DMA 2-slot ring at
 // 4 waves/SIMD 278.5 µs, 3-slot 275.6, register staging 267.4 — although the
 // microbenchmark on random inputs ranked them the other way) nor for dQ
@@ -33,8 +33,24 @@
 // The forward's V tile is only read transposed and uses a swizzle that repeats
 // every 8 rows, so its fragment addresses are per-lane constants plus
 // ds_read immediates (toff_v; 1.6 % on the forward, bitwise-identical output).
+//
+// Variants.  The forward and dQ kernels exist twice, flag FAST (kernel template
+// argument: forward <3> and dQ <1> = FAST, <0> = !FAST; dK/dV once, <1>):
+//   FAST   the shipped path: K/V staged by buffer loads (scalar tile offset),
+//          the wave index in an SGPR, the diagonal tile's triangle masked by
+//          lane-mask constants and its fully masked 32-key half set to −inf
+//          (forward) or skipped (dQ), packed (v_cvt_pk) epilogue; forward: two
+//          v_max3 chains for the tile max, row sums by v_dot2 over the packed
+//          bf16 P, hardware rcp and log; dQ: LDS fragment offsets computed once.
+//   !FAST  the fallback for a (b, h) slice past 31-bit buffer offsets,
+//          S·3·H·64·2 ≥ 2^31 bytes.  K/V staged through 64-bit pointers, and
+//          arithmetic of its own: the mask by per-element compares on the
+//          whole diagonal tile, one max chain, fp32 row sums of the unrounded
+//          P, unpacked epilogue, log2f and 1.f / l.  Its lse and o can differ
+//          from FAST's in the last bits; test_slices_of_2_gib and
+//          test_mask_recovery_past_31_bit_slices (S = 128, H = 43691) hold
+//          it to bit patterns.
 #include <math.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -111,11 +127,9 @@ __device__ __forceinline__ void retire(const bf16x8 (&v)[N]) {
 __device__ __forceinline__ void retire(float x) { asm volatile("" ::"v"(x)); }
 
 // Work order of the (b, h) × block grid: heaviest blocks first across every
-// (b, h) (r = 0 is the heaviest block of the pair).  ``order`` is reserved
-// (0); the XCD-grouped alternative was measured and removed (attn_order).
-__device__ __forceinline__ void attn_block(int order, int nb, int BH, int& bh, int& r) {
-  (void)order;
-  (void)nb;
+// (b, h) (r = 0 is the heaviest block of the pair).  The XCD-grouped alternative
+// was measured and removed (see the launchers).
+__device__ __forceinline__ void attn_block(int BH, int& bh, int& r) {
   const int id = blockIdx.x;
   bh = id % BH;
   r = id / BH;
@@ -149,12 +163,46 @@ __device__ __forceinline__ void stage_load_buf(Stage& st, __amdgpu_buffer_rsrc_t
   for (int i = 0; i < 2; ++i) st.v[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo[i], soff, 0));
 }
 
+// ----- V tile: a transposed-read-only swizzle -----
+// V is only ever read transposed (ds_read_b64_tr_b16, 4 rows × 64 B per
+// 32-lane half).  Rows r and r+2 share banks, so the 16-B chunk index is XORed
+// with 4·bit1(r) only: a row's swizzle then repeats every 8 rows, every
+// transposed fragment of the tile is ONE per-lane base address (two: V columns
+// 0-31 / 32-63) plus a compile-time row offset, i.e. a ds_read immediate — no
+// per-tile address arithmetic.  K keeps the row-read swizzle (toff).
+__device__ __forceinline__ int toff_v(int r, int ch) { return r * HD + ((ch ^ (((r >> 1) & 1) << 2)) << 3); }
+
+// VSWZ: into the V tile's swizzle (toff_v)
+template <bool VSWZ = false>
 __device__ __forceinline__ void stage_store(const Stage& st, bf16* T, int tid) {
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int c = tid + 256 * i, r = c >> 3, ch = c & 7;
-    *reinterpret_cast<bf16x8*>(T + toff(r, ch)) = st.v[i];
+    *reinterpret_cast<bf16x8*>(T + (VSWZ ? toff_v(r, ch) : toff(r, ch))) = st.v[i];
   }
+}
+
+// The forward's and dQ's K/V tile stream: 64-key [K | V] pairs, register-staged
+// into two LDS tile pairs; tile t + 1 is fetched before tile t's MFMAs and
+// committed after them.  Commit: VSWZ = V in its swizzle (the forward).
+template <bool VSWZ>
+__device__ __forceinline__ void kv_commit(const Stage& sk, const Stage& sv, bf16* Kn, int tid) {
+  stage_store(sk, Kn, tid);
+  stage_store<VSWZ>(sv, Kn + TROWS * HD, tid);
+}
+
+// Fetch.  FAST: buffer loads through rk / rv at the per-thread offsets vo plus
+// the tile's byte offset so; the fallback: pointers, rows from row0.  The
+// callers fork: one helper taking both sets changes attn_fwd3_d64<0>.
+__device__ __forceinline__ void kv_fetch(Stage& sk, Stage& sv, __amdgpu_buffer_rsrc_t rk, __amdgpu_buffer_rsrc_t rv,
+                                         const unsigned (&vo)[2], unsigned so) {
+  stage_load_buf(sk, rk, vo, so);
+  stage_load_buf(sv, rv, vo, so);
+}
+__device__ __forceinline__ void kv_fetch(Stage& sk, Stage& sv, const bf16* kbase, const bf16* vbase, size_t rs,
+                                         int row0, int tid) {
+  stage_load(sk, kbase, rs, row0, tid);
+  stage_load(sv, vbase, rs, row0, tid);
 }
 
 // ----- global → LDS by LDS-DMA: no register staging, no ds_write -----
@@ -188,6 +236,32 @@ __device__ __forceinline__ void store_acc_rows(bf16* dst_row, const f32x16& acc,
                 (bf16)(acc[4 * g + 3] * s)};
     *reinterpret_cast<bf16x4*>(dst_row + c0 + 8 * g + 4 * hh) = v;
   }
+}
+
+__device__ __forceinline__ unsigned cvt_pk(float a, float b) {
+  unsigned r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// store_acc_rows with the scale applied to register pairs and packed by v_cvt_pk
+__device__ __forceinline__ void store_acc_rows_pk(bf16* dst_row, const f32x16& acc, int c0, int hh, float s) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    uint2 v;
+    v.x = cvt_pk(acc[4 * g] * s, acc[4 * g + 1] * s);
+    v.y = cvt_pk(acc[4 * g + 2] * s, acc[4 * g + 3] * s);
+    *reinterpret_cast<uint2*>(dst_row + c0 + 8 * g + 4 * hh) = v;
+  }
+}
+
+// l += Σ of the 8 bf16 P values of a B-operand fragment (the values P·V uses)
+__device__ __forceinline__ float rowsum8(bf16x8 p, float acc) {
+  const bf16x2 one = {(bf16)1.f, (bf16)1.f};
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(p, p, 0, 1), one, acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(p, p, 2, 3), one, acc, false);
+  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(p, p, 4, 5), one, acc, false);
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(p, p, 6, 7), one, acc, false);
 }
 
 // Column sums over the workgroup's 128 token rows (the QKV bias gradient,
@@ -241,23 +315,6 @@ __device__ __forceinline__ void colsum_finish(const float* red, float* const (&o
 // ============================================================================
 // forward
 // ============================================================================
-// ----- V tile: a transposed-read-only swizzle -----
-// V is only ever read transposed (ds_read_b64_tr_b16, 4 rows × 64 B per
-// 32-lane half).  Rows r and r+2 share banks, so the 16-B chunk index is XORed
-// with 4·bit1(r) only: a row's swizzle then repeats every 8 rows, every
-// transposed fragment of the tile is ONE per-lane base address (two: V columns
-// 0-31 / 32-63) plus a compile-time row offset, i.e. a ds_read immediate — no
-// per-tile address arithmetic.  K keeps the row-read swizzle (toff).
-__device__ __forceinline__ int toff_v(int r, int ch) { return r * HD + ((ch ^ (((r >> 1) & 1) << 2)) << 3); }
-
-__device__ __forceinline__ void stage_store_v(const Stage& st, bf16* T, int tid) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = tid + 256 * i, r = c >> 3, ch = c & 7;
-    *reinterpret_cast<bf16x8*>(T + toff_v(r, ch)) = st.v[i];
-  }
-}
-
 // per-lane element offset of the tr fragment rows k0 = 0 (lo) for V columns cbase
 __device__ __forceinline__ int tr_base_v(int cbase, int lane) {
   const int g = lane >> 4, t = lane & 15, q = t >> 2, p = t & 3;
@@ -289,31 +346,19 @@ __device__ __forceinline__ constexpr unsigned long long tri_mask_before(int r) {
   return (hi << 32) | lo;
 }
 
-__device__ __forceinline__ unsigned cvt_pk(float a, float b) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// store_acc_rows with the scale applied to register pairs and packed by v_cvt_pk
-__device__ __forceinline__ void store_acc_rows_pk(bf16* dst_row, const f32x16& acc, int c0, int hh, float s) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    uint2 v;
-    v.x = cvt_pk(acc[4 * g] * s, acc[4 * g + 1] * s);
-    v.y = cvt_pk(acc[4 * g + 2] * s, acc[4 * g + 3] * s);
-    *reinterpret_cast<uint2*>(dst_row + c0 + 8 * g + 4 * hh) = v;
-  }
-}
-
-// l += Σ of the 8 bf16 P values of a B-operand fragment (the values P·V uses)
-__device__ __forceinline__ float rowsum8(bf16x8 p, float acc) {
-  const bf16x2 one = {(bf16)1.f, (bf16)1.f};
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(p, p, 0, 1), one, acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(p, p, 2, 3), one, acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(p, p, 4, 5), one, acc, false);
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(p, p, 6, 7), one, acc, false);
-}
+// ----- where the causal diagonal crosses a wave's work (wave-uniform) -----
+// Forward and dQ: wave w holds 32 queries from wave_q0 and walks 64-key tiles.
+// A tile is diagonal when it holds keys after wave_q0; one of its 32-key halves
+// is then the wave's triangle (first key = first query: the first half for an
+// even wave, the second for an odd one), and an even wave's second half follows
+// all its queries: fully masked.
+__device__ __forceinline__ bool tile_on_diagonal(int key0, int wave_q0) { return key0 + TROWS - 1 > wave_q0; }
+__device__ __forceinline__ bool half_is_triangle(int w, int half) { return (w & 1) == half; }
+__device__ __forceinline__ bool half_is_masked(int w, int half) { return half == 1 && !(w & 1); }
+// dK/dV, transposed: the wave holds 32 keys from wave_k0 and walks 32-query
+// blocks; masked = all queries precede the keys, else the first is the triangle
+__device__ __forceinline__ bool qblock_is_masked(int qb0, int wave_k0) { return qb0 + 31 < wave_k0; }
+__device__ __forceinline__ bool qblock_is_triangle(int qb0, int wave_k0) { return qb0 < wave_k0 + 31; }
 
 // ----- attention-probability dropout (DROP instantiations; mask of philox.h) -----
 // A 32 × 32 score block is 8 × 8 patches of 4 queries × 4 keys.  Register group
@@ -364,24 +409,23 @@ __device__ __forceinline__ bf16x8 drop8_q(bf16x8 p, uint32_t ta, uint32_t tb) {
   return __builtin_bit_cast(bf16x8, u);
 }
 
-// Variant bits (A/B in one build, PDO_ATTN_FWDV): 1 = diagonal mask by lane-mask
-// constants (and the fully masked half skipped as −inf), two v_max3 chains
-// for the tile max, packed epilogue; 2 = row sums by v_dot2 over the packed P.
+// FAST: see "Variants" at the top of the file.
 // DROP: dropout of P.  The row maximum, the row sum l and lse stay those of the
 // undropped P; dropped elements are zeroed in the packed fragments that feed
 // P·V and 1/(1 − p) joins the final 1/l.
-template <int V, bool DROP = false>
+template <bool FAST, bool DROP = false>
 __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16* __restrict__ out,
-                                              float* __restrict__ lse, int B, int S, int H, float c2, int order,
+                                              float* __restrict__ lse, int B, int S, int H, float c2,
                                               const DropArgs& da = DropArgs{}) {
-  constexpr bool NEW = V & 1, DOT = V & 2;
   __shared__ __attribute__((aligned(16))) bf16 smem[2 * 2 * TROWS * HD];  // [buf][K|V][64][64]
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, li = lane & 31;
-  const int w = NEW ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
+  const int w = FAST ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   const int nqb = S / 128;
   int bh, r_;
-  attn_block(order, nqb, B * H, bh, r_);
+  attn_block(B * H, bh, r_);
   const int qb = nqb - 1 - r_;  // heaviest query blocks first
+  // the (b, h) slice, spelled out in each body: from a shared helper the
+  // values reach hipcc's first simplification opaque; every prologue changes
   const int b = bh / H, h = bh % H;
   const size_t rs = (size_t)3 * H * HD;
   const bf16* qbase = qkv + (size_t)b * S * rs + (size_t)h * HD;
@@ -402,29 +446,27 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
   float m = 0.f, l = 0.f;
   f32x16 nm16 = zero16();
   const int ntiles = (qb * 128 + 128) / TROWS;
-  const int wave_qmax = qb * 128 + w * 32 + 31;
+  const int wave_q0 = qb * 128 + w * 32, wave_qmax = wave_q0 + 31;
   // DROP: index of the patch this lane draws for the tile at key 0 (philox.h)
   DropPatch<DROP> dpatch;
   if constexpr (DROP)
     dpatch.g = ((uint64_t)bh * (unsigned)(S >> 2) + (unsigned)(q >> 2)) * (unsigned)(S >> 2) + (unsigned)(2 * (li & 3) + hh);
 
+  // the stream's state stays in locals: in a struct it changes every kernel here
   Stage sk, sv;
   unsigned vo[2];
   __amdgpu_buffer_rsrc_t rk, rv;
-  if constexpr (NEW) {
+  if constexpr (FAST) {
     const int nbytes = (int)((size_t)S * rs * 2 - (size_t)H * HD * 2 * 2 - (size_t)h * HD * 2);
     // the builtin, not buf_rsrc: through the helper hipcc orders this kernel's scalar prologue differently
     rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(kbase), 0, nbytes, BUF_RAW32);
     rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(vbase), 0, nbytes, BUF_RAW32);
     stage_voff(vo, rs, tid);
-    stage_load_buf(sk, rk, vo, 0);
-    stage_load_buf(sv, rv, vo, 0);
+    kv_fetch(sk, sv, rk, rv, vo, 0);
   } else {
-    stage_load(sk, kbase, rs, 0, tid);
-    stage_load(sv, vbase, rs, 0, tid);
+    kv_fetch(sk, sv, kbase, vbase, rs, 0, tid);
   }
-  stage_store(sk, smem, tid);
-  stage_store_v(sv, smem + TROWS * HD, tid);
+  kv_commit<true>(sk, sv, smem, tid);
   __syncthreads();
 
   for (int t = 0; t < ntiles; ++t) {
@@ -432,14 +474,10 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
     const bf16* Vt = Kt + TROWS * HD;
     const bool more = t + 1 < ntiles;
     if (more) {
-      if constexpr (NEW) {
-        const unsigned so = (unsigned)((t + 1) * TROWS * rs * 2);
-        stage_load_buf(sk, rk, vo, so);
-        stage_load_buf(sv, rv, vo, so);
-      } else {
-        stage_load(sk, kbase, rs, (t + 1) * TROWS, tid);
-        stage_load(sv, vbase, rs, (t + 1) * TROWS, tid);
-      }
+      if constexpr (FAST)
+        kv_fetch(sk, sv, rk, rv, vo, (unsigned)((t + 1) * TROWS * rs * 2));
+      else
+        kv_fetch(sk, sv, kbase, vbase, rs, (t + 1) * TROWS, tid);
     }
     const int key0 = t * TROWS;
     if (key0 <= wave_qmax) {
@@ -449,11 +487,11 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
         s0 = mfma32(row_frag(Kt, 0, ks, lane), qf[ks], s0);
         s1 = mfma32(row_frag(Kt, 32, ks, lane), qf[ks], s1);
       }
-      if (key0 + TROWS - 1 > qb * 128 + w * 32) {  // diagonal tile (wave-uniform)
-        if constexpr (NEW) {
+      if (tile_on_diagonal(key0, wave_q0)) {
+        if constexpr (FAST) {
           // odd wave: keys of s0 precede every query, s1 is the triangle; even
           // wave: s0 is the triangle, s1 follows every query
-          if (w & 1) {
+          if (half_is_triangle(w, 1)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) s1[r] = __builtin_amdgcn_inverse_ballot_w64(tri_mask(r)) ? -INFINITY : s1[r];
           } else {
@@ -475,7 +513,7 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
       // tile max of s' (relative to m): only a growth past 2^8 rescales
       // (defer-max, cdna_hip_programming.md T13); the first tile sets m
       float tmax;
-      if constexpr (NEW) {
+      if constexpr (FAST) {
         float ta = fmaxf(s0[0], s1[0]), tb = fmaxf(s0[1], s1[1]);
 #pragma unroll
         for (int r = 2; r < 16; r += 2) {
@@ -505,7 +543,7 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
         s1 -= d;
         nm16 = bcast16(-m);
       }
-      if constexpr (DOT) {
+      if constexpr (FAST) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           s0[r] = __builtin_amdgcn_exp2f(s0[r]);
@@ -531,12 +569,12 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
       if constexpr (DROP) {
         const uint64_t gp = dpatch.g + (unsigned)(key0 >> 2);
         quad_keep(attn_patch_keep(da, gp), li & 3, t0.t);
-        if (!(NEW && key0 + TROWS - 1 > qb * 128 + w * 32 && !(w & 1))) quad_keep(attn_patch_keep(da, gp + 8), li & 3, t1.t);
+        if (!(FAST && tile_on_diagonal(key0, wave_q0) && half_is_masked(w, 1))) quad_keep(attn_patch_keep(da, gp + 8), li & 3, t1.t);
       }
       float la = 0.f, lb = 0.f;
       {
         bf16x8 p0 = pack8(s0, 0), p1 = pack8(s1, 0);
-        if constexpr (DOT) {
+        if constexpr (FAST) {
           la = rowsum8(p0, la);
           lb = rowsum8(p1, lb);
         }
@@ -551,7 +589,7 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
       }
       {
         bf16x8 p0 = pack8(s0, 1), p1 = pack8(s1, 1);
-        if constexpr (DOT) {
+        if constexpr (FAST) {
           la = rowsum8(p0, la);
           lb = rowsum8(p1, lb);
         }
@@ -564,18 +602,14 @@ __device__ __forceinline__ void attn_fwd_body(const bf16* __restrict__ qkv, bf16
         o0 = mfma32(tr_frag_v<48>(V0), p1, o0);
         o1 = mfma32(tr_frag_v<48>(V1), p1, o1);
       }
-      if constexpr (DOT) l += la + lb;
+      if constexpr (FAST) l += la + lb;
     }
-    if (more) {
-      bf16* Kn = smem + ((t + 1) & 1) * 2 * TROWS * HD;
-      stage_store(sk, Kn, tid);
-      stage_store_v(sv, Kn + TROWS * HD, tid);
-    }
+    if (more) kv_commit<true>(sk, sv, smem + ((t + 1) & 1) * 2 * TROWS * HD, tid);
     __syncthreads();
   }
   const float lt = xhalf_sum(l);
   bf16* orow = out + ((size_t)(b * S + q) * H + h) * HD;
-  if constexpr (NEW) {
+  if constexpr (FAST) {
     // lt ≥ 1: the key that set m contributes exp2(0)
     float inv = __builtin_amdgcn_rcpf(lt);
     if constexpr (DROP) inv *= da.scale;
@@ -602,7 +636,8 @@ template <int V>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_fwd3_d64(
     const bf16* __restrict__ qkv, bf16* __restrict__ out, float* __restrict__ lse, int B, int S, int H, float c2,
     int order) {
-  attn_fwd_body<V>(qkv, out, lse, B, S, H, c2, order);
+  static_assert(V == 0 || V == 3, "forward variants: 3 = FAST, 0 = the fallback; no others are built");
+  attn_fwd_body<V == 3>(qkv, out, lse, B, S, H, c2);
 }
 // The DROP kernels (forward, dQ, dK/dV) run at 2 waves per SIMD: under the
 // 168-VGPR cap the Philox rounds spill (forward 113, dQ 13, dK/dV 47 VGPRs);
@@ -611,24 +646,26 @@ template <int V>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_fwd3_drop_d64(
     const bf16* __restrict__ qkv, bf16* __restrict__ out, float* __restrict__ lse, int B, int S, int H, float c2,
     int order, DropArgs da) {
-  attn_fwd_body<V, true>(qkv, out, lse, B, S, H, c2, order, da);
+  static_assert(V == 0 || V == 3, "forward variants: 3 = FAST, 0 = the fallback; no others are built");
+  attn_fwd_body<V == 3, true>(qkv, out, lse, B, S, H, c2, da);
 }
 
 // ============================================================================
 // backward dK / dV: workgroup = 128 keys of one (b,h); loop over query tiles
 // ============================================================================
-// V (PDO_ATTN_DKDVV): 1 = each sub-block's 4 Q and 4 dO row fragments read
-// before its first score MFMA (the reads overlap; otherwise every MFMA waits
-// for its own LDS round trip), and the diagonal triangle by lane-mask constants.
+// Each sub-block's Q and dO row fragments are read two k-steps ahead of their
+// score MFMAs and a step's four transposed fragments together (else every
+// MFMA waits for its own LDS round trip: forward + backward 759.4 / 763.0 vs
+// 766.8 / 764.8 µs, round 5, profiles/r5_adamw_resnet_graph.md); the
+// triangle is masked by lane-mask constants.
 // DROP: dV = (keep ∘ P · sd)ᵀ dO with the dropout scale sd applied at the store,
 // dS = P ∘ (keep · sd · (dO·V) − delta).  The dP accumulator then starts at 0
 // (the mask cannot multiply a chain that already holds −delta); −delta is read
 // again from the slot after the MFMAs and joins in one FMA, in fp32.
-template <int V, bool DROP = false>
+template <bool DROP = false>
 __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf16* __restrict__ dout,
-                                          const float* __restrict__ lse, const float* __restrict__ delta,
-                                          bf16* __restrict__ dqkv, int B, int S, int H, float c2,
-                                          float scale, float* __restrict__ dbias_part, int order,
+                                          const float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int S,
+                                          int H, float c2, float scale, float* __restrict__ dbias_part,
                                           const DropArgs& da = DropArgs{}) {
   // ring of 3 slots × {Q [64][64] bf16, dO [64][64] bf16, lse·log2e [64] f32, delta [64] f32}
   constexpr int SLOT = 2 * TROWS * HD + 2 * TROWS * 2;  // bf16 units (16896 B)
@@ -636,7 +673,8 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, li = lane & 31;
   const int nkb = S / 128;
   int bh, kb;
-  attn_block(order, nkb, B * H, bh, kb);  // lowest key blocks have the most query tiles: issue first
+  attn_block(B * H, bh, kb);  // lowest key blocks have the most query tiles: issue first
+  // the (b, h) slice, spelled out per body: see attn_fwd_body
   const int b = bh / H, h = bh % H;
   const size_t rs = (size_t)3 * H * HD;
   const size_t ors = (size_t)H * HD;
@@ -646,7 +684,6 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
   const bf16* dobase = dout + (size_t)b * S * ors + (size_t)h * HD;
   const float* lse2_bh = delta + (size_t)B * H * S + (size_t)bh * S;  // −lse·log2e, written by the dQ kernel
   const float* del_bh = delta + (size_t)bh * S;
-  (void)lse;
 
   const int key = kb * 128 + w * 32 + li;  // this lane's key (column of S / dP)
   bf16x8 kf[4], vf[4];
@@ -661,7 +698,7 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
   f32x16 dv0 = zero16(), dv1 = zero16(), dk0 = zero16(), dk1 = zero16();
   const int qt0 = (kb * 128) / TROWS;
   const int nqt = S / TROWS;
-  const int wave_kmin = kb * 128 + w * 32;
+  const int wave_k0 = kb * 128 + w * 32;
   // DROP: index of the patch this lane draws for the block at query 0 (philox.h);
   // a block at query qb0 adds (qb0 / 4)·(S / 4)
   DropPatch<DROP> dpatch;
@@ -684,25 +721,25 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
   };
   issue(qt0, 0);
   if (qt0 + 1 < nqt) issue(qt0 + 1, 1);
-  int sl = 0;
+  int cur = 0;  // ring slot of tile qt
 
   for (int qt = qt0; qt < nqt; ++qt) {
     if (qt + 1 < nqt)
       vm_wait<5>();  // this wave's pieces of tile qt have landed (qt + 1's 5 may still fly)
     else
       vm_wait<0>();
-    __syncthreads();  // ... and every other wave's; slot (sl + 2) % 3 is free again
-    if (qt + 2 < nqt) issue(qt + 2, sl == 0 ? 2 : sl - 1);
-    const bf16* Qt = smem + sl * SLOT;
+    __syncthreads();  // ... and every other wave's; slot (cur + 2) % 3 is free again
+    if (qt + 2 < nqt) issue(qt + 2, cur == 0 ? 2 : cur - 1);
+    const bf16* Qt = smem + cur * SLOT;
     const bf16* Dt = Qt + TROWS * HD;
     const float* L2 = reinterpret_cast<const float*>(Qt + 2 * TROWS * HD);
     const float* DL = L2 + TROWS;
     const int q0 = qt * TROWS;
-    if (q0 + TROWS - 1 >= wave_kmin) {
+    if (!qblock_is_masked(q0 + 32, wave_k0)) {  // the tile's second block has work
 #pragma unroll
       for (int qs = 0; qs < 2; ++qs) {
         const int qb0 = q0 + 32 * qs;
-        if (qb0 + 31 < wave_kmin) continue;  // all queries before this wave's keys
+        if (qblock_is_masked(qb0, wave_k0)) continue;
         // rows r: q = qb0 + (r&3) + 8(r>>2) + 4hh.  The accumulators start at the
         // rows' −lse·log2e and −delta (stored negated by the dQ kernel): the chains
         // end at s' = c2·q·k − lse·log2e and dp' = dO·v − delta
@@ -721,7 +758,7 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
         KeepBits<DROP> tk;
         if constexpr (DROP)
           quad_keep(attn_patch_keep(da, dpatch.g + (uint64_t)(unsigned)(qb0 >> 2) * (unsigned)(S >> 2)), 8 * (li & 3), tk.t);
-        if constexpr (V == 1) {
+        {
           // two k-steps of fragments in flight (16 VGPRs)
           bf16x8 qa0 = row_frag(Qt, 32 * qs, 0, lane), da0 = row_frag(Dt, 32 * qs, 0, lane);
           bf16x8 qa1 = row_frag(Qt, 32 * qs, 1, lane), da1 = row_frag(Dt, 32 * qs, 1, lane);
@@ -737,12 +774,6 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
           dpacc = mfma32(da0, vf[2], dpacc);
           sacc = mfma32(qa1, kf[3], sacc);
           dpacc = mfma32(da1, vf[3], dpacc);
-        } else {
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            sacc = mfma32(row_frag(Qt, 32 * qs, ks, lane), kf[ks], sacc);
-            dpacc = mfma32(row_frag(Dt, 32 * qs, ks, lane), vf[ks], dpacc);
-          }
         }
         // The causal mask only touches the diagonal sub-tile (wave-uniform): a
         // separate body keeps its compares and selects out of every other tile
@@ -756,14 +787,8 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
             for (int e = 0; e < 4; ++e) {
               const int r = 4 * g + e;
               float p = __builtin_amdgcn_exp2f(sacc[r]);
-              if constexpr (decltype(masked)::value) {
-                if constexpr (V == 1) {
-                  // diagonal block: query c(r) + 4hh (+ qb0) before key li (+ qb0) is masked
-                  p = __builtin_amdgcn_inverse_ballot_w64(tri_mask_before(r)) ? 0.f : p;
-                } else {
-                  p = (q0 + qr + e) < key ? 0.f : p;
-                }
-              }
+              // diagonal block: query c(r) + 4hh (+ qb0) before key li (+ qb0) is masked
+              if constexpr (decltype(masked)::value) p = __builtin_amdgcn_inverse_ballot_w64(tri_mask_before(r)) ? 0.f : p;
               if constexpr (DROP) {
                 const uint32_t km = bit_mask(tk.t[g], e);
                 sacc[r] = and_mask(p, km);
@@ -775,33 +800,25 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
             }
           }
         };
-        if (qb0 < wave_kmin + 31)
+        if (qblock_is_triangle(qb0, wave_k0))
           softmax_grad(std::true_type{});
         else
           softmax_grad(std::false_type{});
 #pragma unroll
         for (int sst = 0; sst < 2; ++sst) {
-          if constexpr (V == 1) {  // the four transposed fragments in flight together
-            const bf16x8 t0 = tr_frag(Dt, 32 * qs + 16 * sst, 0, lane), t1 = tr_frag(Dt, 32 * qs + 16 * sst, 32, lane);
-            const bf16x8 t2 = tr_frag(Qt, 32 * qs + 16 * sst, 0, lane), t3 = tr_frag(Qt, 32 * qs + 16 * sst, 32, lane);
-            const bf16x8 pb = pack8(sacc, sst);
-            const bf16x8 db = pack8(dpacc, sst);
-            dv0 = mfma32(t0, pb, dv0);
-            dv1 = mfma32(t1, pb, dv1);
-            dk0 = mfma32(t2, db, dk0);
-            dk1 = mfma32(t3, db, dk1);
-          } else {
-            const bf16x8 pb = pack8(sacc, sst);
-            const bf16x8 db = pack8(dpacc, sst);
-            dv0 = mfma32(tr_frag(Dt, 32 * qs + 16 * sst, 0, lane), pb, dv0);
-            dv1 = mfma32(tr_frag(Dt, 32 * qs + 16 * sst, 32, lane), pb, dv1);
-            dk0 = mfma32(tr_frag(Qt, 32 * qs + 16 * sst, 0, lane), db, dk0);
-            dk1 = mfma32(tr_frag(Qt, 32 * qs + 16 * sst, 32, lane), db, dk1);
-          }
+          // the four transposed fragments in flight together
+          const bf16x8 t0 = tr_frag(Dt, 32 * qs + 16 * sst, 0, lane), t1 = tr_frag(Dt, 32 * qs + 16 * sst, 32, lane);
+          const bf16x8 t2 = tr_frag(Qt, 32 * qs + 16 * sst, 0, lane), t3 = tr_frag(Qt, 32 * qs + 16 * sst, 32, lane);
+          const bf16x8 pb = pack8(sacc, sst);
+          const bf16x8 db = pack8(dpacc, sst);
+          dv0 = mfma32(t0, pb, dv0);
+          dv1 = mfma32(t1, pb, dv1);
+          dk0 = mfma32(t2, db, dk0);
+          dk1 = mfma32(t3, db, dk1);
         }
       }
     }
-    sl = sl == 2 ? 0 : sl + 1;
+    cur = cur == 2 ? 0 : cur + 1;
   }
   __syncthreads();  // the epilogue's column sums reuse the ring
   // dK = scale * dS^T Q ; dV = P^T dO.  dqkv row `key`, slot 1 (k) and 2 (v)
@@ -832,39 +849,38 @@ __device__ __forceinline__ void dkdv_body(const bf16* __restrict__ qkv, const bf
 // workgroup, allows 3 workgroups per CU)
 template <int V>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_bwd_dkdv3_d64(PDO_DKDV_ARGS) {
-  dkdv_body<V>(qkv, dout, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, order);
+  static_assert(V == 1, "dK/dV has one variant");
+  dkdv_body<>(qkv, dout, delta, dqkv, B, S, H, c2, scale, dbias_part);
 }
 template <int V>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_dkdv3_drop_d64(PDO_DKDV_ARGS,
                                                                                                          DropArgs da) {
-  dkdv_body<V, true>(qkv, dout, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, order, da);
+  static_assert(V == 1, "dK/dV has one variant");
+  dkdv_body<true>(qkv, dout, delta, dqkv, B, S, H, c2, scale, dbias_part, da);
 }
 #undef PDO_DKDV_ARGS
 
 // ============================================================================
 // backward dQ: workgroup = 128 queries of one (b,h); loop over key tiles
 // ============================================================================
-// Variant bits (PDO_ATTN_DQV): 1 = K/V staging by buffer loads (scalar tile
-// offset), per-lane LDS fragment offsets computed once (rows advance in
-// multiples of 16, which the swizzle does not see: the tile loop adds only
-// immediates), the diagonal tile's triangle masked by lane-mask constants and
-// its fully masked 32-key half skipped.
+// FAST ("Variants" at the top) computes its per-lane LDS fragment offsets
+// once: rows advance in multiples of 16, which the swizzle does not see.
 // DROP: the same dS = P ∘ (keep · sd · (dO·V) − delta); delta = rowsum(dO ∘ O) is
 // taken from the dropped O and needs no change.
-template <int V, bool DROP = false>
+template <bool FAST, bool DROP = false>
 __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16* __restrict__ dout,
                                         const bf16* __restrict__ o, const float* __restrict__ lse,
                                         float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int S, int H,
-                                        float c2, float scale, float* __restrict__ dbias_part, int order,
+                                        float c2, float scale, float* __restrict__ dbias_part,
                                         const DropArgs& da = DropArgs{}) {
-  constexpr bool NEW = V & 1;
   __shared__ __attribute__((aligned(16))) bf16 smem[2 * 2 * TROWS * HD];
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, li = lane & 31;
-  const int w = NEW ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
+  const int w = FAST ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   const int nqb = S / 128;
   int bh, r_;
-  attn_block(order, nqb, B * H, bh, r_);
+  attn_block(B * H, bh, r_);
   const int qb = nqb - 1 - r_;
+  // the (b, h) slice, spelled out per body: see attn_fwd_body
   const int b = bh / H, h = bh % H;
   const size_t rs = (size_t)3 * H * HD;
   const size_t ors = (size_t)H * HD;
@@ -909,7 +925,7 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
   // FMA stays)
   f32x16 a0 = zero16(), a1 = zero16();
   const int ntiles = (qb * 128 + 128) / TROWS;
-  const int wave_qmax = qb * 128 + w * 32 + 31;
+  const int wave_q0 = qb * 128 + w * 32, wave_qmax = wave_q0 + 31;
   // DROP: index of the patch this lane draws for the block at key 0 (philox.h)
   DropPatch<DROP> dpatch;
   if constexpr (DROP)
@@ -918,16 +934,15 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
   Stage sk, sv;
   unsigned vo[2];
   __amdgpu_buffer_rsrc_t rk, rv;
-  // per-lane fragment offsets (NEW): row reads roff[ks] = toff(li, 2ks + hh);
+  // per-lane fragment offsets (FAST): row reads roff[ks] = toff(li, 2ks + hh);
   // transposed reads of V-columns half c: rows 4(g>>1) + q (lo) and + 8 (hi)
   int roff[4], tlo[2], thi[2];
-  if constexpr (NEW) {
+  if constexpr (FAST) {
     const int nbytes = (int)((size_t)S * rs * 2 - (size_t)H * HD * 2 * 2 - (size_t)h * HD * 2);
     rk = buf_rsrc(kbase, nbytes);
     rv = buf_rsrc(vbase, nbytes);
     stage_voff(vo, rs, tid);
-    stage_load_buf(sk, rk, vo, 0);
-    stage_load_buf(sv, rv, vo, 0);
+    kv_fetch(sk, sv, rk, rv, vo, 0);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) roff[ks] = toff(li, 2 * ks + hh);
     const int g = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
@@ -938,37 +953,30 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
       thi[c] = toff(r0 + 8, col >> 3) + (col & 7);
     }
   } else {
-    stage_load(sk, kbase, rs, 0, tid);
-    stage_load(sv, vbase, rs, 0, tid);
+    kv_fetch(sk, sv, kbase, vbase, rs, 0, tid);
   }
-  stage_store(sk, smem, tid);
-  stage_store(sv, smem + TROWS * HD, tid);
+  kv_commit<false>(sk, sv, smem, tid);
   __syncthreads();
   for (int t = 0; t < ntiles; ++t) {
     const bool more = t + 1 < ntiles;
     const bf16* Kt = smem + (t & 1) * 2 * TROWS * HD;
     const bf16* Vt = Kt + TROWS * HD;
     if (more) {
-      if constexpr (NEW) {
-        const unsigned so = (unsigned)((t + 1) * TROWS * rs * 2);
-        stage_load_buf(sk, rk, vo, so);
-        stage_load_buf(sv, rv, vo, so);
-      } else {
-        stage_load(sk, kbase, rs, (t + 1) * TROWS, tid);
-        stage_load(sv, vbase, rs, (t + 1) * TROWS, tid);
-      }
+      if constexpr (FAST)
+        kv_fetch(sk, sv, rk, rv, vo, (unsigned)((t + 1) * TROWS * rs * 2));
+      else
+        kv_fetch(sk, sv, kbase, vbase, rs, (t + 1) * TROWS, tid);
     }
     const int key0 = t * TROWS;
     if (key0 <= wave_qmax) {
-      const bool diag = key0 + TROWS - 1 > qb * 128 + w * 32;
+      const bool diag = tile_on_diagonal(key0, wave_q0);
 #pragma unroll
       for (int ksub = 0; ksub < 2; ++ksub) {
-        // diagonal tile: an even wave's second 32 keys follow all its queries
-        if (NEW && ksub == 1 && diag && !(w & 1)) continue;
+        if (FAST && diag && half_is_masked(w, ksub)) continue;
         f32x16 s = zero16(), dp = zero16();
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-          if constexpr (NEW) {
+          if constexpr (FAST) {
             s = mfma32(*reinterpret_cast<const bf16x8*>(Kt + 32 * ksub * HD + roff[ks]), qf[ks], s);
             dp = mfma32(*reinterpret_cast<const bf16x8*>(Vt + 32 * ksub * HD + roff[ks]), df[ks], dp);
           } else {
@@ -983,7 +991,7 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
           for (int r = 0; r < 16; ++r) {
             float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c2, -lq));
             if constexpr (decltype(masked)::value) {
-              if constexpr (NEW) {
+              if constexpr (FAST) {
                 p = __builtin_amdgcn_inverse_ballot_w64(tri_mask(r)) ? 0.f : p;
               } else {
                 const int kr = key0 + 32 * ksub + (r & 3) + 8 * (r >> 2) + 4 * hh;
@@ -996,16 +1004,15 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
               s[r] = p * (dp[r] - dq_delta);  // dS^T
           }
         };
-        // wave-uniform: only the diagonal 32 × 32 block pays for the mask (NEW: the
-        // triangle — the even wave's first half, the odd wave's second)
-        if (NEW ? (diag && (w & 1) == ksub) : diag)
+        // only the diagonal tile pays for the mask (FAST: only its triangle)
+        if (FAST ? (diag && half_is_triangle(w, ksub)) : diag)
           softmax_grad(std::true_type{});
         else
           softmax_grad(std::false_type{});
 #pragma unroll
         for (int sst = 0; sst < 2; ++sst) {
           const bf16x8 dsb = pack8(s, sst);
-          if constexpr (NEW) {
+          if constexpr (FAST) {
             const bf16* T = Kt + (32 * ksub + 16 * sst) * HD;
             a0 = mfma32(ld_tr8(T + tlo[0], T + thi[0]), dsb, a0);
             a1 = mfma32(ld_tr8(T + tlo[1], T + thi[1]), dsb, a1);
@@ -1016,15 +1023,11 @@ __device__ __forceinline__ void dq_body(const bf16* __restrict__ qkv, const bf16
         }
       }
     }
-    if (more) {
-      bf16* Kn = smem + ((t + 1) & 1) * 2 * TROWS * HD;
-      stage_store(sk, Kn, tid);
-      stage_store(sv, Kn + TROWS * HD, tid);
-    }
+    if (more) kv_commit<false>(sk, sv, smem + ((t + 1) & 1) * 2 * TROWS * HD, tid);
     __syncthreads();
   }
   bf16* qrow = dqkv + (size_t)(b * S + q) * rs + (size_t)h * HD;
-  if constexpr (NEW) {
+  if constexpr (FAST) {
     store_acc_rows_pk(qrow, a0, 0, hh, scale);
     store_acc_rows_pk(qrow, a1, 32, hh, scale);
   } else {
@@ -1046,85 +1049,77 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const bf16* __restrict__ qkv, const bf16* __restrict__ dout, const bf16* __restrict__ o,
     const float* __restrict__ lse, float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int S, int H, float c2,
     float scale, float* __restrict__ dbias_part, int order) {
-  dq_body<V>(qkv, dout, o, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, order);
+  static_assert(V == 0 || V == 1, "dQ: 1 = FAST, 0 = the fallback");
+  dq_body<V == 1>(qkv, dout, o, lse, delta, dqkv, B, S, H, c2, scale, dbias_part);
 }
 template <int V>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_dq_drop_d64(
     const bf16* __restrict__ qkv, const bf16* __restrict__ dout, const bf16* __restrict__ o,
     const float* __restrict__ lse, float* __restrict__ delta, bf16* __restrict__ dqkv, int B, int S, int H, float c2,
     float scale, float* __restrict__ dbias_part, int order, DropArgs da) {
-  dq_body<V, true>(qkv, dout, o, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, order, da);
+  dq_body<V == 1, true>(qkv, dout, o, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, da);
 }
 
+// ----- launchers -----
 // Heaviest-first order (attn_block).  The XCD-grouped order cut the kernels'
 // L2 misses 2-3× (forward TCC_EA0_RDREQ 3.1e6 vs 1.05e7 per call) and won the
 // isolated microbenchmark (backward 761 / 754 vs 775 / 777 µs), but lost in
 // the GPT-2-medium step: 144.20 / 144.02 / 144.19 vs 143.88 / 143.78 / 143.81
-// ms (stepab, round 5) — its last workgroups end unevenly; removed in round 6.
-// 4-wave-per-SIMD builds of the forward and dQ spilled and ran 401 / 1068 µs
-// (removed).
-static int attn_order() { return 0; }
+// ms (round 5, profiles/r5_attention_variants.md) — its last workgroups end
+// unevenly; removed in round 6 (the kernels' ``order`` stays, reserved: 0).
+// 4-wave-per-SIMD forward and dQ builds spilled, 401 / 1068 µs (removed).
+
+// -2 / -3 / 0 as kernels.h documents for attn_fwd and attn_bwd
+static int attn_check(int S, int D, const DropArgs* drop) {
+  if (D != HD || S % 128 != 0) return -2;
+  return drop && drop->thr > 255 ? -3 : 0;
+}
+// The kernel of a {FAST, fallback} pair for this shape ("Variants" at the top).
+// The callers name DROP kernels before plain ones and dK/dV after its dQ: hipcc
+// emits the kernels in the order they are first named.
+template <class K>
+static K* attn_variant(K* fast, K* fallback, int S, int H) {
+  return (size_t)S * 3 * H * HD * 2 < (1ull << 31) ? fast : fallback;
+}
 
 int attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int S, int H, int D, float scale, hipStream_t st,
              const DropArgs* drop) {
-  if (D != HD || S % 128 != 0) return -2;
-  // variant 3 (lane-mask diagonal, v_max3 chains, buffer-load staging, v_dot2
-  // row sums, packed epilogue): 285.1 / 289.0 vs 302.6 / 303.1 µs for variant 0
-  // (tools/attn_ab.sh, B64 H16 S1024, 2 interleaved rounds; variant 1 alone
-  // 290.2 / 290.3, variant 2 alone 298.2 / 300.1).  Variant 0 (pointer
-  // staging) remains for a (b, h) slice past 31-bit buffer offsets
+  if (const int rc = attn_check(S, D, drop)) return rc;
   const int grid = B * H * (S / 128);
   const float c2 = scale * LOG2E;
-  // buffer-load variants address the (b, h) slice with 31-bit byte offsets
-  const bool fits = (size_t)S * 3 * H * HD * 2 < (1ull << 31);
-  if (drop && drop->thr) {  // the DROP instantiations of the same two variants
-    if (drop->thr > 255) return -3;
-    if (fits)
-      attn_fwd3_drop_d64<3><<<grid, 256, 0, st>>>(qkv, o, lse, B, S, H, c2, attn_order(), *drop);
-    else
-      attn_fwd3_drop_d64<0><<<grid, 256, 0, st>>>(qkv, o, lse, B, S, H, c2, attn_order(), *drop);
-    return 0;
-  }
-  if (fits)
-    attn_fwd3_d64<3><<<grid, 256, 0, st>>>(qkv, o, lse, B, S, H, c2, attn_order());
+  // FAST: 285.1 / 289.0 vs 302.6 / 303.1 µs for the fallback (B64 H16 S1024, 2
+  // interleaved rounds); without its v_dot2 row sums 290.2 / 290.3, with them
+  // alone 298.2 / 300.1 (round 5, profiles/r5_attention_variants.md).
+  if (drop && drop->thr)
+    attn_variant(attn_fwd3_drop_d64<3>, attn_fwd3_drop_d64<0>, S, H)<<<grid, 256, 0, st>>>(qkv, o, lse, B, S, H, c2, 0,
+                                                                                           *drop);
   else
-    attn_fwd3_d64<0><<<grid, 256, 0, st>>>(qkv, o, lse, B, S, H, c2, attn_order());
+    attn_variant(attn_fwd3_d64<3>, attn_fwd3_d64<0>, S, H)<<<grid, 256, 0, st>>>(qkv, o, lse, B, S, H, c2, 0);
   return 0;
 }
 
 int attn_bwd(const bf16* dout, const bf16* qkv, const bf16* o, const float* lse, float* delta, bf16* dqkv, int B,
              int S, int H, int D, float scale, hipStream_t st, float* dbias_part, const DropArgs* drop) {
-  if (D != HD || S % 128 != 0) return -2;
+  if (const int rc = attn_check(S, D, drop)) return rc;
   const int grid = B * H * (S / 128);
-  if (drop && drop->thr) {  // the DROP instantiations, in the plain kernels' order and variants
-    if (drop->thr > 255) return -3;
-    if ((size_t)S * 3 * H * HD * 2 < (1ull << 31))
-      attn_bwd_dq_drop_d64<1><<<grid, 256, 0, st>>>(qkv, dout, o, lse, delta, dqkv, B, S, H, scale * LOG2E, scale,
-                                                    dbias_part, attn_order(), *drop);
-    else
-      attn_bwd_dq_drop_d64<0><<<grid, 256, 0, st>>>(qkv, dout, o, lse, delta, dqkv, B, S, H, scale * LOG2E, scale,
-                                                    dbias_part, attn_order(), *drop);
-    attn_bwd_dkdv3_drop_d64<1><<<grid, 256, 0, st>>>(qkv, dout, lse, delta, dqkv, B, S, H, scale * LOG2E, scale,
-                                                     dbias_part, attn_order(), *drop);
-    return 0;
+  const float c2 = scale * LOG2E;
+  // dQ first: it also produces delta = rowsum(dO ∘ O), which dK/dV reads.
+  // dQ FAST: forward + backward 772.7 / 769.1 vs 786.9 / 784.3 µs with the
+  // fallback (round 5, profiles/r5_attention_variants.md).  dK/dV (LDS-DMA,
+  // 64-bit addresses: one form for every slice) runs 3 waves per SIMD (168
+  // VGPRs): bwd 799 -> 768 us isolated, -0.55 ms/step against its 2-wave
+  // build.  Round 6 removed that build and the variant without the fragment
+  // prefetch (settled A/Bs).
+  if (drop && drop->thr) {
+    attn_variant(attn_bwd_dq_drop_d64<1>, attn_bwd_dq_drop_d64<0>, S, H)<<<grid, 256, 0, st>>>(
+        qkv, dout, o, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, 0, *drop);
+    attn_bwd_dkdv3_drop_d64<1><<<grid, 256, 0, st>>>(qkv, dout, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, 0,
+                                                     *drop);
+  } else {
+    attn_variant(attn_bwd_dq_d64<1>, attn_bwd_dq_d64<0>, S, H)<<<grid, 256, 0, st>>>(
+        qkv, dout, o, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, 0);
+    attn_bwd_dkdv3_d64<1><<<grid, 256, 0, st>>>(qkv, dout, lse, delta, dqkv, B, S, H, c2, scale, dbias_part, 0);
   }
-  // dQ first: it also produces delta = rowsum(dO ∘ O), which dK/dV reads
-  // variant 1: forward + backward 772.7 / 769.1 vs 786.9 / 784.3 µs with
-  // variant 0 (tools/attn_ab.sh), which remains for slices past 31-bit buffer offsets
-  const bool fits = (size_t)S * 3 * H * HD * 2 < (1ull << 31);
-  if (fits)
-    attn_bwd_dq_d64<1><<<grid, 256, 0, st>>>(qkv, dout, o, lse, delta, dqkv, B, S, H, scale * LOG2E, scale,
-                                             dbias_part, attn_order());
-  else
-    attn_bwd_dq_d64<0><<<grid, 256, 0, st>>>(qkv, dout, o, lse, delta, dqkv, B, S, H, scale * LOG2E, scale,
-                                             dbias_part, attn_order());
-  // 3 waves per SIMD (168 VGPRs): bwd 799 -> 768 us isolated, -0.55 ms/step
-  // against the 2-wave build; variant 1 (fragments prefetched two k-steps / four
-  // transposed reads deep, lane-mask triangle): forward + backward 759.4 / 763.0
-  // vs 766.8 / 764.8 µs (tools/attn_ab.sh).  The 2-wave build and variant 0
-  // were removed in round 6 (settled A/Bs).
-  attn_bwd_dkdv3_d64<1><<<grid, 256, 0, st>>>(qkv, dout, lse, delta, dqkv, B, S, H, scale * LOG2E, scale,
-                                              dbias_part, attn_order());
   return 0;
 }
 
