@@ -471,6 +471,35 @@ void sgd_flat(at::Tensor w, at::Tensor g, at::Tensor buf, at::Tensor decay, doub
                          cur_stream(), lp), "sgd_flat");
 }
 
+// LARS momentum (lars.hip).  table: int32 [T, 3] on w's device, host: its CPU mirror (checked
+// here before any launch); ratio [n / 1024] and part [2·n / 1024]: float32 scratch the caller owns
+void lars_flat(at::Tensor w, at::Tensor g, at::Tensor buf, at::Tensor decay, at::Tensor ratio, at::Tensor part,
+               at::Tensor table, at::Tensor host, double lr, double mom, double wd, double coeff, double eps,
+               double grad_scale, std::optional<at::Tensor> lr_dev) {
+  CHECK_IN(w); CHECK_IN(g); CHECK_IN(buf); CHECK_IN(decay); CHECK_IN(ratio); CHECK_IN(part); CHECK_IN(table);
+  CHECK_F32(w); CHECK_F32(g); CHECK_F32(buf); CHECK_F32(decay); CHECK_F32(ratio); CHECK_F32(part);
+  const long long n = w.numel();
+  TORCH_CHECK(g.numel() == n && buf.numel() == n && n > 0 && n % 1024 == 0 && decay.numel() == n / 1024 &&
+              ratio.numel() == n / 1024 && part.numel() == 2 * (n / 1024), "lars_flat: arena sizes");
+  TORCH_CHECK(table.scalar_type() == at::kInt && table.dim() == 2 && table.size(1) == 3 && table.size(0) >= 1 &&
+              table.device() == w.device(), "lars_flat: table is int32 [T, 3] on w's device");
+  TORCH_CHECK(!host.is_cuda() && host.scalar_type() == at::kInt && host.is_contiguous() &&
+              host.sizes() == table.sizes(), "lars_flat: host table must mirror the device table");
+  for (const at::Tensor* t : {&g, &buf, &decay, &ratio, &part})
+    TORCH_CHECK(t->device() == w.device(), "lars_flat: every tensor on w's device");
+  const float* lp = nullptr;
+  if (lr_dev) {
+    CHECK_IN(*lr_dev); CHECK_F32(*lr_dev);
+    TORCH_CHECK(lr_dev->numel() == 1 && lr_dev->device() == w.device(), "lars_flat: lr_dev is one float on w's device");
+    lp = fp(*lr_dev);
+  }
+  const int rc = pdo::lars_flat(fp(w), fp(g), fp(buf), fp(decay), fp(ratio), fp(part), table.data_ptr<int>(),
+                                host.data_ptr<int>(), (int)table.size(0), n, (float)lr, (float)mom, (float)wd,
+                                (float)coeff, (float)eps, (float)grad_scale, cur_stream(), lp);
+  TORCH_CHECK(rc != -3, "lars_flat: the table does not tile the arena's chunks in order");
+  CHECK_RC(rc, "lars_flat");
+}
+
 // out (+)= sum over the leading dim of part [s, ...] (split-K weight gradients)
 void splitk_add(at::Tensor part, at::Tensor out, bool accumulate) {
   CHECK_IN(part); CHECK_BF16(part); CHECK_BF16(out);
@@ -1726,6 +1755,9 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.def("adamw_flat", &adamw_flat);
   m.def("sgd_flat", &sgd_flat, py::arg("w"), py::arg("g"), py::arg("buf"), py::arg("decay"), py::arg("lr"),
         py::arg("mom"), py::arg("wd"), py::arg("grad_scale"), py::arg("lr_dev") = py::none());
+  m.def("lars_flat", &lars_flat, py::arg("w"), py::arg("g"), py::arg("buf"), py::arg("decay"), py::arg("ratio"),
+        py::arg("part"), py::arg("table"), py::arg("host"), py::arg("lr"), py::arg("mom"), py::arg("wd"),
+        py::arg("coeff"), py::arg("eps"), py::arg("grad_scale"), py::arg("lr_dev") = py::none());
   m.def("splitk_add", &splitk_add);
   m.def("transpose", &transpose, py::arg("x"), py::arg("out") = py::none());
   m.def("transpose_batched", &transpose_batched);

@@ -259,6 +259,16 @@ int sgd_flat(float* w, const float* g, float* buf, const float* decay_chunks, lo
 // lr_dev (optional): the rate is read from this device float instead of `lr` — a schedule
 // under a captured step, where a by-value argument is frozen at capture
 int cast_f32_bf16(const float* in, bf16* out, long long n, hipStream_t st);
+// lars.hip: LARS momentum over the same arena (rule and summation order: the file's header).
+// table (device) and table_host (its host mirror): int [tensors][3] = (first chunk, chunk
+// count, decay flag) of 1,024-element chunks, tiling [0, n / 1024) in order; part: 2·n/1024
+// floats of scratch; ratio_chunks: n/1024 floats, λ of each chunk's tensor on return.
+// w, g, buf zero in every tensor's padding, which stays bitwise zero.  Three launches on
+// st, no synchronisation, no allocation; lr / lr_dev as sgd_flat.  n % 1024: -2, a host
+// table that does not tile the arena: -3, nothing launched.
+int lars_flat(float* w, const float* g, float* buf, const float* decay_chunks, float* ratio_chunks, float* part,
+              const int* table, const int* table_host, int tensors, long long n, float lr, float mom, float wd,
+              float coeff, float eps, float grad_scale, hipStream_t st, const float* lr_dev = nullptr);
 
 // ctr.hip: the CTR models' sparse side; fp32 tables, D % 4 == 0 and 4 <= D <= 64 or -2
 // (sum orders and rounding counts: the file's header)

@@ -80,6 +80,11 @@ def parse_args(argv=None):
                     help="gpt2 / resnet50: optimizer step at which the cosine reaches its floor (default --steps)")
     ap.add_argument("--lr-min-ratio", type=float, default=0.1,
                     help="gpt2 / resnet50: floor of the cosine as a fraction of --lr")
+    ap.add_argument("--optimizer", choices=["sgd", "lars"], default=None,
+                    help="resnet50: momentum SGD (default) or LARS, layer-wise adaptive rate scaling for global "
+                         "batches of 2,048 and above (workloads/resnet.py FlatLARS)")
+    ap.add_argument("--lars-coeff", type=float, default=None,
+                    help="resnet50 with --optimizer lars: the trust coefficient (default 0.001)")
     ap.add_argument("--eval-every", type=int, default=0,
                     help="gpt2: held-out loss, resnet50: held-out loss / top-1 / top-5, on --val-data every N "
                          "optimizer steps (PDO_EVAL records); wide_deep / deepfm without pservers: held-out "
@@ -118,6 +123,10 @@ def parse_args(argv=None):
                  "(PADDLE_PSERVERS_IP_PORT_LIST is set) trains on synthetic batches")
     if args.vocab_per_slot is not None and (not ctr or args.vocab_per_slot < 1):
         ap.error("--vocab-per-slot is a positive row count of the wide_deep / deepfm tables")
+    if args.optimizer == "lars" and args.workload != "resnet50":
+        ap.error("--optimizer lars is built for --workload resnet50 only")
+    if args.lars_coeff is not None and args.optimizer != "lars":
+        ap.error("--lars-coeff needs --optimizer lars")
     args.lr_given = args.lr is not None  # the records carry only flags that were given
     if args.lr is None:
         args.lr = 0.1 if args.workload == "resnet50" else 1e-3 if ctr else 3e-4
@@ -174,7 +183,8 @@ def run_collective(args, jenv) -> int:
                                 lr=args.lr, lr_schedule=args.lr_schedule, lr_warmup=args.lr_warmup,
                                 lr_decay_steps=args.lr_decay_steps or args.steps, lr_min_ratio=args.lr_min_ratio,
                                 data=args.data or None, val_data=args.val_data or None, data_seed=args.data_seed,
-                                data_device_gb=args.data_device_gb)
+                                data_device_gb=args.data_device_gb, optimizer=args.optimizer or "sgd",
+                                lars_coeff=0.001 if args.lars_coeff is None else args.lars_coeff)
         trainer.sync_initial_weights()
         tokens_per_step = trainer.B  # images
     elif args.workload in ("wide_deep", "deepfm"):  # no pserver endpoints (main()): the GPU trainer
@@ -310,6 +320,10 @@ def _resnet_flags(args) -> dict:
         out["lr"] = args.lr
     if args.lr_schedule is not None:
         out["lr_schedule"] = args.lr_schedule
+    if args.optimizer is not None:
+        out["optimizer"] = args.optimizer
+    if args.lars_coeff is not None:
+        out["lars_coeff"] = args.lars_coeff
     return out
 
 

@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from ..models.resnet import resnet18_like_tiny, resnet50
 from ..ops.optim import cosine_lr
 from ..parallel.ddp import BucketedDDP, broadcast_buffers
-from ..parallel.flat import FlatParams
+from ..parallel.flat import ALIGN, FlatParams
 
 
 class FlatSGD:
@@ -69,6 +69,77 @@ class FlatSGD:
         self.step_count = int(sd["step"])
 
 
+class FlatLARS:
+    """LARS momentum (layer-wise adaptive rate scaling, Paddle's ``lars_momentum``) over the
+    flat fp32 arena, fp32 throughout.  With ``g = grad_scale · grad``, per parameter tensor t:
+
+        λ_t = coeff · ‖w_t‖ / (‖g_t‖ + wd·‖w_t‖ + eps)   if t is decayed, ‖w_t‖ > 0 and ‖g_t‖ > 0
+        λ_t = 1                                           otherwise (BatchNorm, biases, zero norms)
+        v ← mom·v + lr·λ_t·(g + wd·dec_t·w),   w ← w − v
+
+    The rate sits inside the velocity here; ``FlatSGD`` applies it outside (``w −= lr·buf``),
+    so the two optimizers' ``buf`` are not interchangeable and ``state_dict`` carries the name.
+
+    On a CUDA fp32 arena one call is three HIP launches on the current stream (csrc/hip/lars.hip
+    ``lars_flat``: per-chunk Σw² / Σg², per-tensor fold to λ, the update), with no host
+    synchronisation and no allocation, so it is captured with the step; with several ranks it
+    runs where ``FlatSGD`` does, after the all-reduce has drained, and every rank computes the
+    same λ.  On CPU, or under ``PDO_OPS=torch``, the rule runs tensor by tensor in torch ops.
+    ``lr_dev`` as in ``FlatSGD``.  ``ratio`` holds λ of each 1,024-element chunk's tensor after
+    a HIP step."""
+
+    name = "lars"
+
+    def __init__(self, flat: FlatParams, lr=0.1, momentum=0.9, weight_decay=5e-5, coeff=0.001, eps=0.0,
+                 lr_dev=None):
+        self.flat, self.lr, self.mom, self.wd = flat, lr, momentum, weight_decay
+        self.coeff, self.eps, self.lr_dev = coeff, eps, lr_dev
+        self.buf = torch.zeros_like(flat.params)
+        self.step_count = 0
+        chunks = flat.numel // ALIGN
+        # (first chunk, chunk count, decay flag) per tensor, in arena order: built once,
+        # read by the fold kernel from the device and checked by the binding on the host
+        rows = [(s.offset // ALIGN, -(-s.numel // ALIGN), int(s.decay)) for s in flat.slots]
+        self.table_host = torch.tensor(rows, dtype=torch.int32)
+        self.table = self.table_host.to(flat.params.device)
+        self.ratio = torch.ones(chunks, dtype=torch.float32, device=flat.params.device)
+        self._part = torch.zeros(2 * chunks, dtype=torch.float32, device=flat.params.device)
+
+    @torch.no_grad()
+    def step(self, grad_scale=1.0):
+        from .. import _native
+        f, g = self.flat, self.flat.param_grads
+        if g.is_cuda and g.dtype == torch.float32 and _native.ops_mode() != "torch":
+            _native.require_hip().lars_flat(f.params, g, self.buf, f.decay_chunks, self.ratio, self._part, self.table,
+                                            self.table_host, self.lr, self.mom, self.wd, self.coeff, self.eps,
+                                            grad_scale, self.lr_dev)
+            self.step_count += 1
+            return
+        lr = self.lr_dev if self.lr_dev is not None else self.lr
+        for s in f.slots:
+            w = f.params[s.offset:s.offset + s.numel]
+            v = self.buf[s.offset:s.offset + s.numel]
+            gt = g[s.offset:s.offset + s.numel] * grad_scale
+            wn, gn = w.norm(), gt.norm()
+            lam = torch.ones_like(wn)
+            if s.decay:
+                lam = torch.where((wn > 0) & (gn > 0), self.coeff * wn / (gn + self.wd * wn + self.eps), lam)
+                gt = gt + self.wd * w
+            v.mul_(self.mom).add_(lr * lam * gt)
+            w.sub_(v)
+        self.step_count += 1
+
+    def state_dict(self):
+        return {"buf": self.buf, "step": self.step_count, "optimizer": self.name}
+
+    def load_state_dict(self, sd):
+        if sd.get("optimizer") != self.name:
+            raise ValueError(f"optimizer state of {sd.get('optimizer', 'sgd')!r} loaded into {self.name!r}: "
+                             "the velocity holds the rate here and not there")
+        self.buf.copy_(sd["buf"])
+        self.step_count = int(sd["step"])
+
+
 class ResNetTrainer:
     """``graph=True``: after two eager warm-up steps the whole training step
     (weight cast, forward, loss, backward, SGD update) is captured once into a
@@ -86,14 +157,22 @@ class ResNetTrainer:
     1-float device tensor before it, outside the graph, and both the eager and the
     captured update read that tensor — ``cosine_lr(opt.step_count, lr, lr_warmup,
     lr_decay_steps, lr_min_ratio)`` for cosine.  ``None``: ``lr`` travels by value.
-    ``classes`` defaults to 1000 (10 for tiny)."""
+    ``classes`` defaults to 1000 (10 for tiny).
+
+    ``optimizer``: ``"sgd"`` (``FlatSGD``) or ``"lars"`` (``FlatLARS`` with ``lars_coeff`` /
+    ``lars_eps``, the large-batch recipe); eager, captured and multi-rank steps run either.  A
+    LARS checkpoint records the optimizer's name, and a checkpoint of one optimizer does not
+    load into the other."""
 
     def __init__(self, batch: int, device, tiny: bool = False, bucket_mb: int = 25, channels_last: bool = True,
                  graph: bool = False, lr: float = 0.1, lr_schedule: str | None = None, lr_warmup: int = 0,
                  lr_decay_steps: int = 10000, lr_min_ratio: float = 0.1, data: str | None = None,
                  val_data: str | None = None, data_seed: int = 0, data_device_gb: float = 8.0,
-                 classes: int | None = None):
+                 classes: int | None = None, optimizer: str = "sgd", lars_coeff: float = 0.001,
+                 lars_eps: float = 0.0):
         from .. import _native
+        if optimizer not in ("sgd", "lars"):
+            raise ValueError(f"optimizer must be sgd or lars, not {optimizer!r}")
         if lr_schedule not in (None, "constant", "cosine"):
             raise ValueError(f"lr_schedule must be None, constant or cosine, not {lr_schedule!r}")
         if _native.ops_mode() == "torch":  # the framework reference path: MIOpen convolutions
@@ -116,7 +195,11 @@ class ResNetTrainer:
         self.lr_warmup, self.lr_decay_steps, self.lr_min_ratio = int(lr_warmup), int(lr_decay_steps), lr_min_ratio
         # with a schedule the update reads its rate from this tensor (FlatSGD lr_dev)
         self.lr_dev = torch.full((1,), lr, dtype=torch.float32, device=self.device) if lr_schedule else None
-        self.opt = FlatSGD(self.flat, lr=lr, lr_dev=self.lr_dev)
+        self.optimizer = optimizer
+        if optimizer == "lars":
+            self.opt = FlatLARS(self.flat, lr=lr, coeff=lars_coeff, eps=lars_eps, lr_dev=self.lr_dev)
+        else:
+            self.opt = FlatSGD(self.flat, lr=lr, lr_dev=self.lr_dev)
         self.res = 32 if tiny else 224
         self.data = self.val = None
         rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
@@ -263,10 +346,16 @@ class ResNetTrainer:
                 d.close()
 
     def state_dict(self):
-        return {"params": self.flat.params, "opt_buf": self.opt.buf, "step": self.opt.step_count,
-                "buffers": {k: v for k, v in self.model.named_buffers()}}
+        sd = {"params": self.flat.params, "opt_buf": self.opt.buf, "step": self.opt.step_count,
+              "buffers": {k: v for k, v in self.model.named_buffers()}}
+        if self.optimizer != "sgd":  # an SGD checkpoint is what it always was
+            sd["optimizer"] = self.optimizer
+        return sd
 
     def load_state_dict(self, sd):
+        saved = sd.get("optimizer", "sgd")
+        if saved != self.optimizer:  # the velocity holds the rate under LARS and not under SGD
+            raise ValueError(f"checkpoint written with --optimizer {saved}, this trainer runs {self.optimizer}")
         self.flat.params.copy_(sd["params"].to(self.flat.params.device))
         self.opt.buf.copy_(sd["opt_buf"].to(self.opt.buf.device))
         bufs = dict(self.model.named_buffers())

@@ -77,7 +77,9 @@ def hip_flags(name):
     agpr_files = {"gemm_nt4.hip", "gemm_dw4.hip"}
     # per-file extras: attention's softmax max-reductions become v_max3 only
     # without NaN canonicalisation (scores are never NaN; ±inf masks keep working)
-    extra = {"attention.hip": ["-fno-honor-nans"]}
+    # lars.hip: no packed fp32 instructions (v_pk_fma_f32 and kin) in its f32x4 arithmetic
+    extra = {"attention.hip": ["-fno-honor-nans"],
+             "lars.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
     form = [] if name in agpr_files else vgpr_form
     return common + form + extra.get(name, [])
 
