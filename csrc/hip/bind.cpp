@@ -637,6 +637,58 @@ at::Tensor gemm_nt(at::Tensor a, at::Tensor b, c10::optional<at::Tensor> bias, c
   return c;
 }
 
+// ---- e4m3 forward GEMM (quant_f8.hip, gemm_nt_f8.hip) ----
+// rows × cols view of a 1-D / 2-D tensor whose last dimension is dense (a column slice keeps its row stride)
+static void rows_view(const at::Tensor& t, const char* what, int64_t& rows, int64_t& cols, int64_t& ld) {
+  TORCH_CHECK(t.is_cuda() && (t.dim() == 1 || t.dim() == 2) && t.numel() > 0 && t.stride(-1) == 1, what,
+              ": a non-empty GPU vector or matrix with dense rows");
+  rows = t.dim() == 2 ? t.size(0) : 1;
+  cols = t.size(-1);
+  ld = t.dim() == 2 && rows > 1 ? t.stride(0) : cols;
+}
+
+// per-tensor power-of-two e4m3 quantisation: (bytes shaped like x, 2^−e as a float[1]); no host sync
+std::tuple<at::Tensor, at::Tensor> quant_e4m3(at::Tensor x) {
+  CHECK_BF16(x);
+  int64_t rows, cols, ld;
+  rows_view(x, "quant_e4m3", rows, cols, ld);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "quant_e4m3: x must be 16-byte aligned");
+  at::Tensor q = at::empty(x.sizes(), x.options().dtype(at::kByte));
+  at::Tensor ws = at::empty({2}, x.options().dtype(at::kFloat));  // [amax bits, 2^−e]
+  unsigned* amax = reinterpret_cast<unsigned*>(fp(ws));
+  CHECK_RC(pdo::amax_bf16(bp(x), rows, cols, ld, amax, cur_stream()), "amax_bf16");
+  CHECK_RC(pdo::quant_e4m3(bp(x), rows, cols, ld, amax, q.data_ptr<uint8_t>(), cols, fp(ws) + 1, cur_stream()), "quant_e4m3");
+  return {q, ws.narrow(0, 1, 1)};
+}
+
+bool gemm_nt_f8_supported(int64_t M, int64_t N, int64_t K) {
+  return M < (1LL << 31) && N < (1LL << 31) && K < (1LL << 31) &&
+         pdo::gemm_nt_f8_ok((int)M, (int)N, (int)K, (int)K, (int)K, (int)N);
+}
+
+// c = bf16((qa·qbᵀ)·da·db (+ bias)): qa [M, K], qb [N, K] e4m3 bytes (dense rows, any row stride the kernel takes)
+at::Tensor gemm_nt_f8(at::Tensor qa, at::Tensor da, at::Tensor qb, at::Tensor db, c10::optional<at::Tensor> bias) {
+  int64_t M, K, lda, N, Kb, ldb;
+  rows_view(qa, "gemm_nt_f8", M, K, lda);
+  rows_view(qb, "gemm_nt_f8", N, Kb, ldb);
+  TORCH_CHECK(qa.scalar_type() == at::kByte && qb.scalar_type() == at::kByte && qa.dim() == 2 && qb.dim() == 2 && K == Kb,
+              "gemm_nt_f8: qa [M, K], qb [N, K] uint8");
+  CHECK_IN(da); CHECK_F32(da); CHECK_IN(db); CHECK_F32(db);
+  TORCH_CHECK(da.numel() == 1 && db.numel() == 1, "gemm_nt_f8: da, db are one float each");
+  TORCH_CHECK(M < (1LL << 31) && N < (1LL << 31) && lda < (1LL << 31) && ldb < (1LL << 31) &&
+                  reinterpret_cast<uintptr_t>(qa.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(qb.data_ptr()) % 16 == 0,
+              "gemm_nt_f8: operands must be 16-byte aligned and below 2^31 rows");
+  const bf16* bptr = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN((*bias)); CHECK_BF16((*bias)); TORCH_CHECK(bias->numel() == N);
+    bptr = bp(*bias);
+  }
+  at::Tensor c = at::empty({M, N}, qa.options().dtype(at::kBFloat16));
+  CHECK_RC(pdo::gemm_nt_f8(qa.data_ptr<uint8_t>(), fp(da), qb.data_ptr<uint8_t>(), fp(db), (int)M, (int)N, (int)K, (int)lda,
+                           (int)ldb, bp(c), (int)N, bptr ? pdo::EPI_BIAS : pdo::EPI_PLAIN, bptr, cur_stream()), "gemm_nt_f8");
+  return c;
+}
+
 // c = a·bᵀ (+ bias) + r (r: [M, N] contiguous bf16), one pass; one rounding on the 4-wave mainloop
 at::Tensor gemm_nt_add(at::Tensor a, at::Tensor b, at::Tensor r, c10::optional<at::Tensor> bias,
                        c10::optional<at::Tensor> mask) {
@@ -1794,6 +1846,9 @@ PYBIND11_MODULE(_pdo_hip, m) {
     return prev;
   }, py::arg("on") = -1, "gemm_nt4 tile order: 1 = dynamic per-XCD counters, 0 = static (default); returns the previous");
   m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(), py::arg("out") = py::none());
+  m.def("quant_e4m3", &quant_e4m3, py::arg("x"));
+  m.def("gemm_nt_f8_supported", &gemm_nt_f8_supported);
+  m.def("gemm_nt_f8", &gemm_nt_f8, py::arg("qa"), py::arg("da"), py::arg("qb"), py::arg("db"), py::arg("bias") = py::none());
   m.def("gemm_nt_gelu", &gemm_nt_gelu, py::arg("a"), py::arg("b"), py::arg("bias"), py::arg("saved_grad") = false);
   m.def("gemm_nt_dgelu", &gemm_nt_dgelu, py::arg("a"), py::arg("b"), py::arg("pre"), py::arg("bias"),
         py::arg("db_out") = py::none(), py::arg("saved_grad") = false);

@@ -221,6 +221,21 @@ void gemm_nt_set_impl(int impl);
 // gemm_nt4 tile order: 1 = dynamic per-XCD counters, 0 = static (default; experiments only)
 void gemm_nt4_set_dynamic(int on);
 int gemm_nt_get_impl();
+// quant_f8.hip: per-tensor power-of-two e4m3 quantisation of x[rows][cols] bf16 (row stride ld ≥ cols), two passes.
+// amax_bf16: max |x| as a float's bit pattern into *amax_out (cleared by a one-lane kernel in front: no memset node,
+// no host sync, no allocation).  quant_e4m3: s = 2^e, e = 8 − a (m ≤ 1.75) or 7 − a from amax = m·2^a (exponent and
+// mantissa bits; amax = 0 → e = 0; |e| ≤ 126), q[r][c] (row stride ldq) = RNE_e4m3(x·s), *dscale_out = 2^−e.
+// rows > 1: cols, ld, ldq % 8 = 0; one row (or ld = ldq = cols): any length.  x 16-B, q 8-B aligned.  Finite inputs.
+int amax_bf16(const bf16* x, long long rows, long long cols, long long ld, unsigned* amax_out, hipStream_t st);
+int quant_e4m3(const bf16* x, long long rows, long long cols, long long ld, const unsigned* amax, unsigned char* q,
+               long long ldq, float* dscale_out, hipStream_t st);
+// gemm_nt_f8.hip: C[M][N] = bf16((A[M][K]·B[N][K]ᵀ)·da·db (+ bias[N])), A / B e4m3 bytes, da / db device floats, fp32
+// accumulation, one rounding.  M % 256 = 0, N % 256 ∈ {0, 128}, K % 256 = 0 (≥ 256), lda / ldb % 16 = 0 and ≥ K
+// (A, B 16-B aligned), ldc % 4 = 0 and ≥ N: else -2, nothing launched.  epi: EPI_PLAIN or EPI_BIAS (-3 without bias);
+// any other value -4, as gemm_nt() answers "no such epilogue".
+int gemm_nt_f8_ok(int M, int N, int K, int lda, int ldb, int ldc);
+int gemm_nt_f8(const unsigned char* A, const float* da, const unsigned char* B, const float* db, int M, int N, int K,
+               int lda, int ldb, bf16* C, int ldc, int epi, const bf16* bias, hipStream_t st);
 // transpose.hip: out[C][R] = in[R][C], R and C multiples of 64
 int transpose_bf16(const bf16* in, bf16* out, int R, int C, hipStream_t st);
 // every matrix of a table in one launch: table = n × {first tile, src offset, dst

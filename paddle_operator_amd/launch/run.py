@@ -48,6 +48,9 @@ def parse_args(argv=None):
                     help="gpt2: attention-probability dropout inside the flash-attention kernels (quantised to 1/256; "
                          "default 0)")
     ap.add_argument("--dropout-seed", type=int, default=0, help="gpt2: seed of the dropout masks")
+    ap.add_argument("--fp8", default=None, choices=["off", "qkv"],
+                    help="gpt2: forward products on FP8 (e4m3) operands with bf16 gradients; qkv = the QKV projection "
+                         "(default off)")
     ap.add_argument("--data", default=os.environ.get("PDO_TRAIN_DATA", ""),
                     help="gpt2: training token file, raw little-endian uint16 ids (nanoGPT train.bin); resnet50: "
                          "directory with images.npy (uint8 [n, R, R, 3]) and labels.npy ([n]); wide_deep / deepfm "
@@ -168,6 +171,8 @@ def run_collective(args, jenv) -> int:
         cfg = GPT2Config.named("gpt2-tiny" if args.tiny else args.model)
         cfg.embd_pdrop = cfg.resid_pdrop = args.dropout
         cfg.attn_pdrop = args.attn_dropout
+        if args.fp8 is not None:
+            cfg.fp8 = args.fp8
         seq = min(args.seq, cfg.n_positions)
         trainer = GPT2Trainer(cfg, args.batch or (2 if args.tiny else 32), seq, dev, lr=args.lr,
                               dropout_seed=args.dropout_seed, grad_accum=args.grad_accum or 1,
@@ -307,6 +312,8 @@ def _gpt2_flags(args) -> dict:
         out["grad_accum"] = args.grad_accum
     if args.lr_schedule is not None:
         out["lr_schedule"] = args.lr_schedule
+    if args.fp8 is not None:
+        out["fp8"] = args.fp8
     return out
 
 

@@ -53,9 +53,15 @@ class GPT2Config:
     embd_pdrop: float = 0.0
     resid_pdrop: float = 0.0
     attn_pdrop: float = 0.0
+    # forward products on FP8 (e4m3) operands, gradients stay bf16: "off" | "qkv" (the QKV projection, ops.linear_fp8)
+    fp8: str = "off"
     # 128: 50304 rows.  256 (PDO_PAD_VOCAB=256): 50432, full 256-wide tiles, so the
     # LM head's forward / dX GEMMs enter gemm_nt4 and its dW gemm_dw4's full-height tiles
     pad_vocab_to: int = field(default_factory=lambda: int(os.environ.get("PDO_PAD_VOCAB", "128")))
+
+    def __post_init__(self):
+        if self.fp8 not in ("off", "qkv"):
+            raise ValueError(f"GPT2Config.fp8 must be 'off' or 'qkv', got {self.fp8!r}")
 
     @property
     def padded_vocab(self) -> int:
@@ -133,7 +139,8 @@ class Block(nn.Module):
         LayerNorm reads the stream once.
         """
         cfg = self.cfg
-        a = ops.qkv_attention(h, self.qkv.weight, self.qkv.bias, cfg.n_head, drop=drop_prob)
+        a = ops.qkv_attention(h, self.qkv.weight, self.qkv.bias, cfg.n_head, drop=drop_prob,
+                              fp8=cfg.fp8 == "qkv")
         x, h2 = ops.linear_add_layer_norm(a, self.proj.weight, self.proj.bias, x, self.ln2_w, self.ln2_b,
                                           cfg.ln_eps, drop_attn)
         return ops.mlp_add_layer_norm(h2, self.fc.weight, self.fc.bias, self.fc_proj.weight, self.fc_proj.bias,
