@@ -121,13 +121,22 @@ static pdo::DropArgs drop_args(int64_t thr, uint64_t seed, int64_t site, int64_t
 }
 
 // ---------------------------------------------------------------- layernorm
-std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b, double eps) {
+// q8: the result gains (q, dscale) — each row of y as e4m3 bytes [N, C] under its own power-of-two scale, and
+// 2^−e per row as float32 [N] (ops.ref_quant_e4m3 of the row) — written by the same kernel
+std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b, double eps, bool q8) {
   CHECK_IN(x); CHECK_IN(w); CHECK_IN(b); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(b);
   TORCH_CHECK(x.dim() == 2 && w.numel() == x.size(1) && b.numel() == x.size(1));
   const int N = x.size(0), C = x.size(1);
   auto y = at::empty_like(x);
   auto mean = at::empty({N}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({N}, x.options().dtype(at::kFloat));
+  if (q8) {
+    auto q = at::empty({N, C}, x.options().dtype(at::kByte));
+    auto ds = at::empty({N}, x.options().dtype(at::kFloat));
+    CHECK_RC(pdo::layernorm_fwd_q8(bp(x), nullptr, nullptr, bp(w), bp(b), nullptr, bp(y), fp(mean), fp(rstd),
+                                   q.data_ptr<uint8_t>(), fp(ds), N, C, (float)eps, cur_stream()), "layernorm_fwd");
+    return {y, mean, rstd, q, ds};
+  }
   CHECK_RC(pdo::layernorm_fwd(bp(x), nullptr, nullptr, bp(w), bp(b), nullptr, bp(y), fp(mean), fp(rstd), N, C,
                               (float)eps, cur_stream()), "layernorm_fwd");
   return {y, mean, rstd};
@@ -136,7 +145,7 @@ std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b, 
 // thr > 0: h = x + drop(r + rbias)
 std::vector<at::Tensor> add_layernorm_fwd(at::Tensor x, c10::optional<at::Tensor> r_, at::Tensor w, at::Tensor b,
                                           double eps, c10::optional<at::Tensor> rbias, int64_t thr, uint64_t seed,
-                                          int64_t site, int64_t step, uint64_t offset) {
+                                          int64_t site, int64_t step, uint64_t offset, bool q8) {
   TORCH_CHECK(r_.has_value(), "add_layernorm_fwd: rbias and dropout apply to the residual branch r, which is "
               "missing (layernorm_fwd is the LayerNorm without one)");
   const at::Tensor& r = *r_;
@@ -155,6 +164,14 @@ std::vector<at::Tensor> add_layernorm_fwd(at::Tensor x, c10::optional<at::Tensor
   auto y = at::empty_like(x);
   auto mean = at::empty({N}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({N}, x.options().dtype(at::kFloat));
+  if (q8) {  // + (q, dscale), as layernorm_fwd
+    auto q = at::empty({N, C}, x.options().dtype(at::kByte));
+    auto ds = at::empty({N}, x.options().dtype(at::kFloat));
+    CHECK_RC(pdo::layernorm_fwd_q8(bp(x), bp(r), rb, bp(w), bp(b), bp(h), bp(y), fp(mean), fp(rstd),
+                                   q.data_ptr<uint8_t>(), fp(ds), N, C, (float)eps, cur_stream(), &drop),
+             "add_layernorm_fwd");
+    return {h, y, mean, rstd, q, ds};
+  }
   CHECK_RC(pdo::layernorm_fwd(bp(x), bp(r), rb, bp(w), bp(b), bp(h), bp(y), fp(mean), fp(rstd), N, C, (float)eps,
                               cur_stream(), &drop), "add_layernorm_fwd");
   return {h, y, mean, rstd};
@@ -666,27 +683,47 @@ bool gemm_nt_f8_supported(int64_t M, int64_t N, int64_t K) {
          pdo::gemm_nt_f8_ok((int)M, (int)N, (int)K, (int)K, (int)K, (int)N);
 }
 
-// c = bf16((qa·qbᵀ)·da·db (+ bias)): qa [M, K], qb [N, K] e4m3 bytes (dense rows, any row stride the kernel takes)
-at::Tensor gemm_nt_f8(at::Tensor qa, at::Tensor da, at::Tensor qb, at::Tensor db, c10::optional<at::Tensor> bias) {
+// c = bf16((qa·qbᵀ)·da·db (+ bias)): qa [M, K], qb [N, K] e4m3 bytes (dense rows, any row stride the kernel takes);
+// da one float, or M floats = one scale per row of qa (the per-token scales a LayerNorm wrote).
+// gelu (the row form only): (gelu', gelu) of the fp32 (qa·qbᵀ)·da[m]·db + bias, as gemm_nt_gelu(saved_grad=true)
+static std::vector<at::Tensor> f8_run(const char* what, at::Tensor qa, at::Tensor da, at::Tensor qb, at::Tensor db,
+                                      c10::optional<at::Tensor> bias, bool gelu) {
   int64_t M, K, lda, N, Kb, ldb;
-  rows_view(qa, "gemm_nt_f8", M, K, lda);
-  rows_view(qb, "gemm_nt_f8", N, Kb, ldb);
+  rows_view(qa, what, M, K, lda);
+  rows_view(qb, what, N, Kb, ldb);
   TORCH_CHECK(qa.scalar_type() == at::kByte && qb.scalar_type() == at::kByte && qa.dim() == 2 && qb.dim() == 2 && K == Kb,
-              "gemm_nt_f8: qa [M, K], qb [N, K] uint8");
+              what, ": qa [M, K], qb [N, K] uint8");
   CHECK_IN(da); CHECK_F32(da); CHECK_IN(db); CHECK_F32(db);
-  TORCH_CHECK(da.numel() == 1 && db.numel() == 1, "gemm_nt_f8: da, db are one float each");
+  const bool rows = da.numel() == M;  // (M = 1 is outside the kernel's contract)
+  TORCH_CHECK((da.numel() == 1 || rows) && db.numel() == 1, what, ": da is one float or one per row of qa, db one float");
+  TORCH_CHECK(rows || !gelu, what, ": the GELU epilogue takes per-row scales (da of M floats)");
   TORCH_CHECK(M < (1LL << 31) && N < (1LL << 31) && lda < (1LL << 31) && ldb < (1LL << 31) &&
-                  reinterpret_cast<uintptr_t>(qa.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(qb.data_ptr()) % 16 == 0,
-              "gemm_nt_f8: operands must be 16-byte aligned and below 2^31 rows");
+                  reinterpret_cast<uintptr_t>(qa.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(qb.data_ptr()) % 16 == 0 &&
+                  (!rows || reinterpret_cast<uintptr_t>(da.data_ptr()) % 16 == 0),
+              what, ": operands (and per-row scales) must be 16-byte aligned and below 2^31 rows");
   const bf16* bptr = nullptr;
   if (bias.has_value()) {
     CHECK_IN((*bias)); CHECK_BF16((*bias)); TORCH_CHECK(bias->numel() == N);
     bptr = bp(*bias);
   }
   at::Tensor c = at::empty({M, N}, qa.options().dtype(at::kBFloat16));
-  CHECK_RC(pdo::gemm_nt_f8(qa.data_ptr<uint8_t>(), fp(da), qb.data_ptr<uint8_t>(), fp(db), (int)M, (int)N, (int)K, (int)lda,
-                           (int)ldb, bp(c), (int)N, bptr ? pdo::EPI_BIAS : pdo::EPI_PLAIN, bptr, cur_stream()), "gemm_nt_f8");
-  return c;
+  at::Tensor y;
+  if (gelu) y = at::empty({M, N}, c.options());
+  const int epi = gelu ? pdo::EPI_GELU_SAVE_GRAD : bptr ? pdo::EPI_BIAS : pdo::EPI_PLAIN;
+  const int rc = pdo::gemm_nt_f8(qa.data_ptr<uint8_t>(), fp(da), qb.data_ptr<uint8_t>(), fp(db), (int)M, (int)N, (int)K,
+                                 (int)lda, (int)ldb, bp(c), (int)N, epi, bptr, cur_stream(), rows, gelu ? bp(y) : nullptr,
+                                 (int)N);
+  TORCH_CHECK(rc == 0, what, " rejected the shape (code ", rc, ")");
+  if (gelu) return {c, y};
+  return {c};
+}
+
+at::Tensor gemm_nt_f8(at::Tensor qa, at::Tensor da, at::Tensor qb, at::Tensor db, c10::optional<at::Tensor> bias) {
+  return f8_run("gemm_nt_f8", qa, da, qb, db, bias, false)[0];
+}
+
+std::vector<at::Tensor> gemm_nt_f8_gelu(at::Tensor qa, at::Tensor da, at::Tensor qb, at::Tensor db, at::Tensor bias) {
+  return f8_run("gemm_nt_f8_gelu", qa, da, qb, db, bias, true);
 }
 
 // c = a·bᵀ (+ bias) + r (r: [M, N] contiguous bf16), one pass; one rounding on the 4-wave mainloop
@@ -1778,10 +1815,10 @@ bool enable_peer_access(int peer) {
 
 PYBIND11_MODULE(_pdo_hip, m) {
   m.doc() = "paddle_operator_amd HIP/CDNA4 kernels (gfx950)";
-  m.def("layernorm_fwd", &layernorm_fwd);
+  m.def("layernorm_fwd", &layernorm_fwd, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("eps"), py::arg("q8") = false);
   m.def("add_layernorm_fwd", &add_layernorm_fwd, py::arg("x"), py::arg("r"), py::arg("w"), py::arg("b"),
         py::arg("eps"), py::arg("rbias") = py::none(), py::arg("thr") = 0, py::arg("seed") = 0, py::arg("site") = 0,
-        py::arg("step") = 0, py::arg("offset") = 0);
+        py::arg("step") = 0, py::arg("offset") = 0, py::arg("q8") = false);
   m.def("layernorm_bwd", &layernorm_bwd, py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),
         py::arg("rstd"), py::arg("grads") = py::none());
   m.def("layernorm_bwd_add", &layernorm_bwd_add, py::arg("dy"), py::arg("h"), py::arg("w"), py::arg("mean"),
@@ -1849,6 +1886,7 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.def("quant_e4m3", &quant_e4m3, py::arg("x"));
   m.def("gemm_nt_f8_supported", &gemm_nt_f8_supported);
   m.def("gemm_nt_f8", &gemm_nt_f8, py::arg("qa"), py::arg("da"), py::arg("qb"), py::arg("db"), py::arg("bias") = py::none());
+  m.def("gemm_nt_f8_gelu", &gemm_nt_f8_gelu, py::arg("qa"), py::arg("da"), py::arg("qb"), py::arg("db"), py::arg("bias"));
   m.def("gemm_nt_gelu", &gemm_nt_gelu, py::arg("a"), py::arg("b"), py::arg("bias"), py::arg("saved_grad") = false);
   m.def("gemm_nt_dgelu", &gemm_nt_dgelu, py::arg("a"), py::arg("b"), py::arg("pre"), py::arg("bias"),
         py::arg("db_out") = py::none(), py::arg("saved_grad") = false);

@@ -1,7 +1,18 @@
 // SPDX-License-Identifier: Apache-2.0
 // C[M][N] = bf16((A[M][K] · B[N][K]ᵀ) · da · db (+ bias[N])) on gfx950, A and B
 // OCP e4m3 bytes (quant_f8.hip), da / db device floats (powers of two), fp32
-// accumulation, one rounding at the bf16 store.  EPI_PLAIN and EPI_BIAS only.
+// accumulation, one rounding at the bf16 store.  EPI_PLAIN and EPI_BIAS.
+//
+// Row form (gemm_nt_f8_kernel<EPI, true>): da holds M floats, one per row of A — the
+// per-token scales of the e4m3 rows a LayerNorm wrote (layernorm.hip, Q8); db
+// stays one float.  The store is still one fma, C = bf16(fma(acc, da[m]·db,
+// bias)); da[m]·db is an exact power of two while it stays normal (both are
+// 2^−e with |e| ≤ 126, so the product can leave the normal range only when
+// both operands are extreme — then it rounds like any fp32 product).  A lane's
+// rows are mr + 16i + e: per i the four da[mr + 16i .. + 3] are one 16-B load,
+// requested before the tile's last k-tile.  On this form the kernel also has
+// fc1's epilogue EPI_GELU_SAVE_GRAD, as gemm_nt4 stores it: x = fma(acc, da[m]·db,
+// bias), C = bf16(gelu'(x)), Y = bf16(gelu(x)) (common.h, gelu_and_grad2).
 //
 // Work split: gemm_nt4's — 256 × 256 output tile, 4 waves, one per SIMD, each
 // owning a 128 × 128 block as 64 16×16 accumulators pinned to the accumulator
@@ -69,21 +80,36 @@ __device__ __forceinline__ void mfma_f8_acc0(f32x4& c, const i32x8& a, const i32
   asm volatile("v_mfma_f32_16x16x128_f8f6f4 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
 }
 
-template <int EPI>
+// the epilogues this kernel has: the plain stores on either scale form, fc1's on the row form
+constexpr bool epi_f8(int e, bool rows) { return epi_plain_store(e) || (rows && e == EPI_GELU_SAVE_GRAD); }
+static_assert(epi_f8(EPI_PLAIN, false) && epi_f8(EPI_BIAS, false) && !epi_f8(EPI_GELU_SAVE_GRAD, false) &&
+              epi_f8(EPI_PLAIN, true) && epi_f8(EPI_BIAS, true) && epi_f8(EPI_GELU_SAVE_GRAD, true) &&
+              !epi_f8(EPI_GELU, true) && !epi_f8(EPI_BIAS_ADD, true) && !epi_f8(EPI_STATS, true),
+              "gemm_nt_f8's epilogue list");
+
+struct NoOut {};  // the trailing kernel argument of the scalar form
+struct RowsOut {  // of the row form: EPI_GELU_SAVE_GRAD's second output
+  bf16* Y;
+  int ldy;
+};
+
+// ROWS = false: da is one float; true: M floats, one per row of A (per token)
+template <int EPI, bool ROWS = false>
 __global__ __launch_bounds__(NTHR, 1) void gemm_nt_f8_kernel(const unsigned char* __restrict__ A,
                                                              const unsigned char* __restrict__ B, int lda, int ldb,
                                                              int M, int N, int nk, bf16* __restrict__ C, int ldc,
                                                              const bf16* __restrict__ bias,
                                                              const float* __restrict__ da,
-                                                             const float* __restrict__ db, int group_m) {
-  static_assert(epi_plain_store(EPI), "no such epilogue");
+                                                             const float* __restrict__ db, int group_m,
+                                                             std::conditional_t<ROWS, RowsOut, NoOut> yo) {
+  static_assert(epi_f8(EPI, ROWS), "no such epilogue");
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 2 * OPB];  // [buf][A|B][256][128]
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w >> 1, wn = w & 1;
   const int tiles_n = (N + BN - 1) / BN;  // N % 256 = 128 allowed (half-width last tile column)
   const int nwg = (M / BM) * tiles_n;
-  const float scale = da[0] * db[0];  // exact: powers of two
+  const float scale = ROWS ? db[0] : da[0] * db[0];  // exact: powers of two (ROWS: da[m] joins in the epilogue)
   // gemm_nt4's tile order: XCD-contiguous ids, group_m tile rows per column step
   auto coords = [&](int v, int& tm_, int& tn_) {
     const int id = xcd_remap(v, nwg);
@@ -190,14 +216,26 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt_f8_kernel(const unsigned char
   };
   // acc[i][j][e] = product[m][n], m = wm·128 + 16i + 4(l >> 4) + e, n = wn·128 +
   // 8(l & 15) + j: per (i, e) a lane stores 8 consecutive columns, non-temporal
+  // ROWS: the tile's row scales, one 16-B load per i (rows mr + 16i .. + 3 of this lane), requested before the
+  // tile's last k-tile so that they arrive under its 64 MFMAs (M % 256 = 0: every row exists)
+  f32x4 dav[ROWS ? 8 : 1];
+  auto load_row_scales = [&]() {
+    if constexpr (ROWS) {
+      const float* p = da + (m0 + wm * 128 + 4 * g4);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) dav[i] = *reinterpret_cast<const f32x4*>(p + 16 * i);
+    }
+  };
   auto row_epilogue = [&]() {
     asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");  // XDL D → v_accvgpr_read (hipcc does not pad the asm)
     if (halfn && wn == 1) return;
     const int nb = n0 + wn * 128 + 8 * (lane & 15);
     const size_t mr = (size_t)(m0 + wm * 128 + 4 * g4);
     f32x8 bv8 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if constexpr (EPI == EPI_BIAS) bv8 = to_f32(*reinterpret_cast<const bf16x8*>(bias + nb));
+    if constexpr (epi_needs_bias(EPI)) bv8 = to_f32(*reinterpret_cast<const bf16x8*>(bias + nb));
     const f32x8 sc8 = {scale, scale, scale, scale, scale, scale, scale, scale};
+    f32x2 m1 = {-1.f, -1.f};
+    if constexpr (EPI == EPI_GELU_SAVE_GRAD) asm volatile("" : "+v"(m1));  // common.h, gelu_sig_grad2
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       f32x4 a[8];
@@ -206,9 +244,32 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt_f8_kernel(const unsigned char
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const f32x8 v = {a[0][e], a[1][e], a[2][e], a[3][e], a[4][e], a[5][e], a[6][e], a[7][e]};
-        // one fma: the scaled product joins the bias unrounded
-        const bf16x8 o = to_bf16(__builtin_elementwise_fma(v, sc8, bv8));
-        __builtin_nontemporal_store(o, reinterpret_cast<bf16x8*>(C + (mr + 16 * i + e) * ldc + nb));
+        if constexpr (!ROWS) {
+          // one fma: the scaled product joins the bias unrounded
+          const bf16x8 o = to_bf16(__builtin_elementwise_fma(v, sc8, bv8));
+          __builtin_nontemporal_store(o, reinterpret_cast<bf16x8*>(C + (mr + 16 * i + e) * ldc + nb));
+          continue;
+        }
+        const float s = dav[ROWS ? i : 0][e] * scale;  // da[m]·db
+        const f32x8 x = __builtin_elementwise_fma(v, f32x8{s, s, s, s, s, s, s, s}, bv8);
+        bf16* crow = C + (mr + 16 * i + e) * ldc + nb;
+        if constexpr (EPI == EPI_GELU_SAVE_GRAD) {
+          // fc1 as gemm_nt4 stores it: C = gelu'(x), Y = gelu(x), x the fp32 pre-activation
+          f32x8 y, g;
+#pragma unroll
+          for (int q = 0; q < 8; q += 2) {
+            f32x2 yy, gg;
+            gelu_and_grad2(f32x2{x[q], x[q + 1]}, m1, yy, gg);
+            y[q] = yy[0];
+            y[q + 1] = yy[1];
+            g[q] = gg[0];
+            g[q + 1] = gg[1];
+          }
+          __builtin_nontemporal_store(to_bf16(g), reinterpret_cast<bf16x8*>(crow));
+          __builtin_nontemporal_store(to_bf16(y), reinterpret_cast<bf16x8*>(yo.Y + (mr + 16 * i + e) * yo.ldy + nb));
+        } else {
+          __builtin_nontemporal_store(to_bf16(x), reinterpret_cast<bf16x8*>(crow));
+        }
       }
     }
   };
@@ -231,6 +292,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt_f8_kernel(const unsigned char
     const bool has_next = vnext < nwg;
     int ntm = tm, ntn = tn;
     if (has_next) coords(vnext, ntm, ntn);
+    load_row_scales();
     step(B1{}, F_{}, srcs(ntm * BM, ntn * BN, 0), has_next);  // the next tile's k-tile 0 under this one's last
     row_epilogue();
     if (!has_next) break;
@@ -262,15 +324,27 @@ int gemm_nt_f8_ok(int M, int N, int K, int lda, int ldb, int ldc) {
 }
 
 int gemm_nt_f8(const unsigned char* A, const float* da, const unsigned char* B, const float* db, int M, int N, int K,
-               int lda, int ldb, bf16* C, int ldc, int epi, const bf16* bias, hipStream_t st) {
+               int lda, int ldb, bf16* C, int ldc, int epi, const bf16* bias, hipStream_t st, bool da_rows, bf16* Y,
+               int ldy) {
   if (!gemm_nt_f8_ok(M, N, K, lda, ldb, ldc)) return -2;
-  if (!da || !db || (epi == EPI_BIAS && !bias)) return -3;
+  if (!da || !db || (da_rows && reinterpret_cast<uintptr_t>(da) % 16)) return -3;
+  // gemm_nt()'s verdict on the epilogue's own arguments (bias, Y, ldy); the 4-wave-only fc1 epilogue exists here
+  // on the row form alone
+  if (epi_f8(epi, true))
+    if (const int rc = gemm_nt_args_rc(epi, bias != nullptr, Y != nullptr, ldy, N, false, da_rows)) return rc;
   const long long tiles = (long long)(M / BM) * ((N + BN - 1) / BN);
   if (tiles > 0x7fffffffLL) return -2;
   constexpr int group_m = 4;  // gemm_nt4's
   const int g = persistent_grid(tiles);
+  if (da_rows)
+    return nt_epi_dispatch(std::integer_sequence<int, EPI_PLAIN, EPI_BIAS, EPI_GELU_SAVE_GRAD>{}, epi, [&](auto e) {
+      gemm_nt_f8_kernel<decltype(e)::value, true><<<g, NTHR, 0, st>>>(A, B, lda, ldb, M, N, K / BK, C, ldc, bias, da, db,
+                                                                      group_m, RowsOut{Y, ldy});
+      return 0;
+    });
   return nt_epi_dispatch(std::integer_sequence<int, EPI_PLAIN, EPI_BIAS>{}, epi, [&](auto e) {
-    gemm_nt_f8_kernel<decltype(e)::value><<<g, NTHR, 0, st>>>(A, B, lda, ldb, M, N, K / BK, C, ldc, bias, da, db, group_m);
+    gemm_nt_f8_kernel<decltype(e)::value><<<g, NTHR, 0, st>>>(A, B, lda, ldb, M, N, K / BK, C, ldc, bias, da, db, group_m,
+                                                              NoOut{});
     return 0;
   });
 }

@@ -32,6 +32,11 @@ struct ColOut {
 int layernorm_fwd(const bf16* x, const bf16* r, const bf16* rb, const bf16* w, const bf16* b, bf16* h, bf16* y,
                   float* mean, float* rstd, int N, int C, float eps, hipStream_t st,
                   const DropArgs* drop = nullptr);
+// the same call (same contract: C % 8 = 0, C ≤ 4096) that also writes q8[N][C] = the e4m3 bytes of each row of the
+// bf16 y under the row's own power-of-two scale (quant_f8.hip's rule per row) and dscale[N] = 2^−e; -3 without them
+int layernorm_fwd_q8(const bf16* x, const bf16* r, const bf16* rb, const bf16* w, const bf16* b, bf16* h, bf16* y,
+                     float* mean, float* rstd, unsigned char* q8, float* dscale, int N, int C, float eps,
+                     hipStream_t st, const DropArgs* drop = nullptr);
 int layernorm_bwd_grid(int N);
 // out: where dgamma | dbeta | (drbias) go (ColOut segments of C columns)
 // reduce = false: only the partial rows are written (the caller reduces part later)
@@ -232,10 +237,13 @@ int quant_e4m3(const bf16* x, long long rows, long long cols, long long ld, cons
 // gemm_nt_f8.hip: C[M][N] = bf16((A[M][K]·B[N][K]ᵀ)·da·db (+ bias[N])), A / B e4m3 bytes, da / db device floats, fp32
 // accumulation, one rounding.  M % 256 = 0, N % 256 ∈ {0, 128}, K % 256 = 0 (≥ 256), lda / ldb % 16 = 0 and ≥ K
 // (A, B 16-B aligned), ldc % 4 = 0 and ≥ N: else -2, nothing launched.  epi: EPI_PLAIN or EPI_BIAS (-3 without bias);
-// any other value -4, as gemm_nt() answers "no such epilogue".
+// any other value -4, as gemm_nt() answers "no such epilogue".  da_rows: da is M floats (16-B aligned), one scale per
+// row of A, C[m][n] = bf16(acc·(da[m]·db) (+ bias[n])); this form also takes EPI_GELU_SAVE_GRAD with gemm_nt4's
+// outputs (C = gelu', Y = gelu of acc·da[m]·db + bias; Y, ldy as gemm_nt_args_rc asks: ldy % 4 = 0 and ≥ N).
 int gemm_nt_f8_ok(int M, int N, int K, int lda, int ldb, int ldc);
 int gemm_nt_f8(const unsigned char* A, const float* da, const unsigned char* B, const float* db, int M, int N, int K,
-               int lda, int ldb, bf16* C, int ldc, int epi, const bf16* bias, hipStream_t st);
+               int lda, int ldb, bf16* C, int ldc, int epi, const bf16* bias, hipStream_t st, bool da_rows = false,
+               bf16* Y = nullptr, int ldy = 0);
 // transpose.hip: out[C][R] = in[R][C], R and C multiples of 64
 int transpose_bf16(const bf16* in, bf16* out, int R, int C, hipStream_t st);
 // every matrix of a table in one launch: table = n × {first tile, src offset, dst

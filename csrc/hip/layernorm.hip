@@ -12,7 +12,15 @@
 // the forward, the same call again in the backward, no stored mask.  The
 // DROP = false instantiations are the kernels as they were (the DropArgs
 // argument is last and unread).
+//
+// Q8 instantiations (ln_fwd_kernel<..., true>, all three forms): the forward also writes the row
+// as e4m3 bytes with one power-of-two scale per token, the A operand of the FP8
+// QKV / fc1 products (gemm_nt_f8.hip, row scales) — no quantise pass, no state.
+// Everything else they write is bit for bit what the plain kernels write.
+#include <type_traits>
+
 #include "common.h"
+#include "f8_quant.h"
 #include "kernels.h"
 
 namespace pdo {
@@ -25,13 +33,25 @@ __device__ __forceinline__ f32x8 drop_apply(f32x8 v, uint32_t keep, float scale)
   return o;
 }
 
-template <int VPL, bool ADD, bool DROP = false>
+struct NoOut {};  // the trailing kernel argument of the instantiations without extra outputs
+struct Q8Out {
+  unsigned char* q;  // [N][C] e4m3 bytes
+  float* dscale;     // [N] 2^−e of each row
+};
+
+// Q8 (trailing argument Q8Out, else the empty NoOut): the row is also written as e4m3 bytes with
+// its own power-of-two scale — quant_f8.hip's per-tensor rule applied to this row of the
+// bf16-ROUNDED output, (q[row], dscale[row]) == ref_quant_e4m3(y[row]).  A lane keeps its rounded
+// outputs (VPL × 4 registers) across the wave-wide max of their 15 low bits; columns without data
+// contribute 0 and store nothing; each 16-B bf16 vector becomes one 8-B store.
+template <int VPL, bool ADD, bool DROP = false, bool Q8 = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16* __restrict__ x, const bf16* __restrict__ r,
                                                      const bf16* __restrict__ rb,
                                                      const bf16* __restrict__ w, const bf16* __restrict__ b,
                                                      bf16* __restrict__ h, bf16* __restrict__ y,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                     int N, int C, float eps, DropArgs drop) {
+                                                     int N, int C, float eps, DropArgs drop,
+                                                     std::conditional_t<Q8, Q8Out, NoOut> qo) {
   static_assert(ADD || !DROP, "dropout applies to the residual branch");
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -79,6 +99,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16* __restrict__ x,
   const float rstd = rsqrtf(wave_sum(q) * inv_c + eps);
   const bf16x8* wr = reinterpret_cast<const bf16x8*>(w);
   const bf16x8* br = reinterpret_cast<const bf16x8*>(b);
+  bf16x8 yb[Q8 ? VPL : 1];
+  u16x8 am = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int c8 = lane + i * 64;
@@ -86,12 +108,34 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16* __restrict__ x,
       if (ADD) reinterpret_cast<bf16x8*>(h + base)[c8] = to_bf16(v[i]);
       f32x8 wf = to_f32(wr[c8]), bf = to_f32(br[c8]);
       f32x8 o = (v[i] - mean) * rstd * wf + bf;
-      reinterpret_cast<bf16x8*>(y + base)[c8] = to_bf16(o);
+      if constexpr (Q8) {
+        yb[i] = to_bf16(o);
+        reinterpret_cast<bf16x8*>(y + base)[c8] = yb[i];
+        am = __builtin_elementwise_max(am, __builtin_bit_cast(u16x8, yb[i]) & (unsigned short)0x7fff);
+      } else {
+        reinterpret_cast<bf16x8*>(y + base)[c8] = to_bf16(o);
+      }
     }
   }
   if (lane == 0) {
     mean_out[row] = mean;
     rstd_out[row] = rstd;
+  }
+  if constexpr (Q8) {
+    // |y| of a finite bf16 orders like its 15 low bits: the row's amax as a float's bit pattern
+    unsigned a = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a = max(a, (unsigned)am[k]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a = max(a, (unsigned)__shfl_xor((int)a, o, 64));
+    const int e = f8_scale_exp(a << 16);
+    const float s = f8_pow2(e);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const int c8 = lane + i * 64;
+      if (c8 < C8) reinterpret_cast<i32x2*>(qo.q + base)[c8] = f8_cvt8(to_f32(yb[i]) * s);  // y·s exact in fp32
+    }
+    if (lane == 0) qo.dscale[row] = f8_pow2(-e);
   }
 }
 
@@ -242,12 +286,36 @@ int layernorm_fwd(const bf16* x, const bf16* r, const bf16* rb, const bf16* w, c
   const int vpl = vpl_for(C);
   const DropArgs d = drop ? *drop : DropArgs();
   if (d.thr) {
-    LN_DISPATCH(vpl, ln_fwd_kernel<V, true, true><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps, d))
+    LN_DISPATCH(vpl, ln_fwd_kernel<V, true, true><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps, d, NoOut{}))
   } else if (r) {
-    LN_DISPATCH(vpl, ln_fwd_kernel<V, true><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps, d))
+    LN_DISPATCH(vpl, ln_fwd_kernel<V, true><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps, d, NoOut{}))
   } else {
-    LN_DISPATCH(vpl, ln_fwd_kernel<V, false><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps, d))
+    LN_DISPATCH(vpl, ln_fwd_kernel<V, false><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps, d, NoOut{}))
   }
+  return 0;
+}
+
+int layernorm_fwd_q8(const bf16* x, const bf16* r, const bf16* rb, const bf16* w, const bf16* b, bf16* h, bf16* y,
+                     float* mean, float* rstd, unsigned char* q8, float* dscale, int N, int C, float eps,
+                     hipStream_t st, const DropArgs* drop) {
+  if (C % 8 != 0 || C > 4096) return -2;
+  if (rb && !r) return -4;
+  if (drop && (drop->thr > 65535u || (drop->thr && !r))) return -6;
+  if (!q8 || !dscale) return -3;
+  const int grid = (N + 3) / 4;
+  const int vpl = vpl_for(C);
+  const DropArgs d = drop ? *drop : DropArgs();
+  const Q8Out qo{q8, dscale};
+#define LN_Q8(ADD_, DROP_) \
+  LN_DISPATCH(vpl, ln_fwd_kernel<V, ADD_, DROP_, true><<<grid, 256, 0, st>>>(x, r, rb, w, b, h, y, mean, rstd, N, C, eps, d, qo))
+  if (d.thr) {
+    LN_Q8(true, true)
+  } else if (r) {
+    LN_Q8(true, false)
+  } else {
+    LN_Q8(false, false)
+  }
+#undef LN_Q8
   return 0;
 }
 

@@ -13,12 +13,13 @@
 //
 // Scale s = 2^e from amax = m·2^a, m ∈ [1, 2): e = 8 − a for m ≤ 1.75, else
 // 7 − a, so amax·s ∈ (224, 448] (448 = the largest finite e4m3).  e comes from
-// the exponent and mantissa BITS (f8_scale_exp), which a host reference
+// the exponent and mantissa BITS (f8_scale_exp, f8_quant.h), which a host reference
 // reproduces exactly; amax = 0 → e = 0; e is clamped to ±126 so s and 1/s are
 // normal.  x·s is exact in fp32 and the hardware convert (v_cvt_pk_fp8_f32,
 // OCP e4m3fn on gfx950) rounds to nearest even: 16 B of bf16 in, 8 B of fp8 out
 // per lane.  Only finite inputs are specified.
 #include "common.h"
+#include "f8_quant.h"
 #include "kernels.h"
 
 namespace pdo {
@@ -26,16 +27,6 @@ namespace pdo {
 namespace {
 
 constexpr int NTHR = 256;
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int f8_scale_exp(unsigned amax_bits) {
-  if (amax_bits == 0u) return 0;
-  const int a = (int)(amax_bits >> 23) - 127;
-  const int e = ((amax_bits & 0x7fffffu) <= 0x600000u ? 8 : 7) - a;
-  return e < -126 ? -126 : e > 126 ? 126 : e;
-}
-
 // vector v of the matrix → element offsets in x (stride ld) and q (stride ldq)
 struct RowMap {
   unsigned vpr;  // 16-B vectors per row
@@ -79,12 +70,7 @@ __global__ __launch_bounds__(NTHR) void quant_e4m3_kernel(const bf16* __restrict
     long long xo, qo;
     rm.at(v, xo, qo);
     const f32x8 f = to_f32(*reinterpret_cast<const bf16x8*>(x + xo)) * s;
-    i32x2 o = {0, 0};
-    o[0] = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], o[0], false);
-    o[0] = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], o[0], true);
-    o[1] = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], o[1], false);
-    o[1] = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], o[1], true);
-    *reinterpret_cast<i32x2*>(q + qo) = o;
+    *reinterpret_cast<i32x2*>(q + qo) = f8_cvt8(f);
   }
   if (blockIdx.x == 0 && (int)threadIdx.x < tail) {
     const long long i = 8ll * nvec + threadIdx.x;

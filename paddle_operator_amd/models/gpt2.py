@@ -53,15 +53,17 @@ class GPT2Config:
     embd_pdrop: float = 0.0
     resid_pdrop: float = 0.0
     attn_pdrop: float = 0.0
-    # forward products on FP8 (e4m3) operands, gradients stay bf16: "off" | "qkv" (the QKV projection, ops.linear_fp8)
+    # forward products on FP8 (e4m3) operands, gradients stay bf16: "off" | "qkv" (the QKV projection, quantised
+    # per tensor just in time, ops.linear_fp8) | "ln" (QKV and fc1 from e4m3 rows that the producing LayerNorm
+    # writes with one scale per token, ops.linear_fp8_rows)
     fp8: str = "off"
     # 128: 50304 rows.  256 (PDO_PAD_VOCAB=256): 50432, full 256-wide tiles, so the
     # LM head's forward / dX GEMMs enter gemm_nt4 and its dW gemm_dw4's full-height tiles
     pad_vocab_to: int = field(default_factory=lambda: int(os.environ.get("PDO_PAD_VOCAB", "128")))
 
     def __post_init__(self):
-        if self.fp8 not in ("off", "qkv"):
-            raise ValueError(f"GPT2Config.fp8 must be 'off' or 'qkv', got {self.fp8!r}")
+        if self.fp8 not in ("off", "qkv", "ln"):
+            raise ValueError(f"GPT2Config.fp8 must be 'off', 'qkv' or 'ln', got {self.fp8!r}")
 
     @property
     def padded_vocab(self) -> int:
@@ -126,7 +128,8 @@ class Block(nn.Module):
         self.fc = Linear(C, 4 * C)
         self.fc_proj = Linear(4 * C, C)
 
-    def forward(self, x, h, ln_next_w, ln_next_b, drop_attn=None, drop_mlp=None, drop_prob=None):
+    def forward(self, x, h, ln_next_w, ln_next_b, drop_attn=None, drop_mlp=None, drop_prob=None, f8=None,
+                q8_next=False):
         """x: residual stream, h: LN1(x) already computed by the caller.
         ``drop_attn`` / ``drop_mlp``: residual dropout of the two branches
         (ops.core.Dropout or None), ``drop_prob``: the spec of the
@@ -137,14 +140,20 @@ class Block(nn.Module):
         output projection's GEMM epilogue (bias and residual added there,
         ops.linear_add_layer_norm / ops.mlp_add_layer_norm) and the following
         LayerNorm reads the stream once.
+
+        ``f8`` (fp8 = "ln"): h as e4m3 rows with per-token scales, written by the
+        LayerNorm that produced it; LN2 then writes h2's rows for fc1, and with
+        ``q8_next`` the result gains LN_next's rows for the next block:
+        (x_out, LN_next(x_out), (q, d)).
         """
         cfg = self.cfg
         a = ops.qkv_attention(h, self.qkv.weight, self.qkv.bias, cfg.n_head, drop=drop_prob,
-                              fp8=cfg.fp8 == "qkv")
-        x, h2 = ops.linear_add_layer_norm(a, self.proj.weight, self.proj.bias, x, self.ln2_w, self.ln2_b,
-                                          cfg.ln_eps, drop_attn)
+                              fp8=cfg.fp8 == "qkv", f8=f8)
+        x, h2, *f8_2 = ops.linear_add_layer_norm(a, self.proj.weight, self.proj.bias, x, self.ln2_w, self.ln2_b,
+                                                 cfg.ln_eps, drop_attn, q8=f8 is not None)
         return ops.mlp_add_layer_norm(h2, self.fc.weight, self.fc.bias, self.fc_proj.weight, self.fc_proj.bias,
-                                      x, ln_next_w, ln_next_b, cfg.ln_eps, drop_mlp)
+                                      x, ln_next_w, ln_next_b, cfg.ln_eps, drop_mlp, f8=f8_2[0] if f8_2 else None,
+                                      q8=q8_next)
 
 
 class GPT2(nn.Module):
@@ -204,15 +213,19 @@ class GPT2(nn.Module):
         d0 = self._drop(cfg.embd_pdrop, 0)
         x = ops.embedding(idx, self.wte, self.wpe, d0, masked_grad=True)
         blk0 = self.blocks[0]
-        x, h = ops.layer_norm_res(x, blk0.ln1_w, blk0.ln1_b, cfg.ln_eps, d0)
+        # fp8 = "ln": every LayerNorm that feeds a block's QKV / fc1 also writes its rows as e4m3 (the final one,
+        # which feeds the LM head, does not); outside the FP8 GEMM's shape contract nothing is asked and bf16 runs
+        q8 = cfg.fp8 == "ln" and ops.ln_q8_ok(x, blk0.qkv.weight, blk0.fc.weight)
+        x, h, *f8 = ops.layer_norm_res(x, blk0.ln1_w, blk0.ln1_b, cfg.ln_eps, d0, q8=q8)
         for i, blk in enumerate(self.blocks):
             da, dm = self._drop(cfg.resid_pdrop, 1 + 2 * i), self._drop(cfg.resid_pdrop, 2 + 2 * i)
             dp = self._drop_attn(i)
+            pair = f8[0] if f8 else None
             if i + 1 < len(self.blocks):
                 nb = self.blocks[i + 1]
-                x, h = blk(x, h, nb.ln1_w, nb.ln1_b, da, dm, dp)
+                x, h, *f8 = blk(x, h, nb.ln1_w, nb.ln1_b, da, dm, dp, pair, q8)
             else:
-                x, h = blk(x, h, self.lnf_w, self.lnf_b, da, dm, dp)
+                x, h = blk(x, h, self.lnf_w, self.lnf_b, da, dm, dp, pair, False)
         if targets is None:
             return ops.linear(h, self.wte)[..., :cfg.vocab_size]
         return ops.lm_head_xent(h, self.wte, targets, cfg.vocab_size)

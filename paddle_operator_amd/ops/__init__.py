@@ -2,7 +2,8 @@
 
 * ``ops.core``   — dispatch, fp32 references, arena gradient hand-off,
   ``linear``, the batched Wᵀ and deferred column sums;
-* ``ops.fp8``    — e4m3 quantisation and the FP8 forward product (``linear_fp8``);
+* ``ops.fp8``    — e4m3 quantisation and the FP8 forward product (``linear_fp8``; ``linear_fp8_rows`` on the
+  e4m3 rows a LayerNorm wrote, one scale per token);
 * ``ops.gpt2``   — LayerNorm, MLP, attention, LM head + cross-entropy, embedding;
 * ``ops.resnet`` — convolutions, BatchNorm, the stem;
 * ``ops.optim``  — the fused flat AdamW;
@@ -19,7 +20,9 @@ from .core import (  # noqa: F401
     ref_cross_entropy, ref_layer_norm, transpose, use_hip,
     Dropout, dropout_spec, dropout_thr, philox4x32_10, philox_keep_mask, ref_dropout,
     ATTN_SITE0, attn_dropout_spec, attn_dropout_thr, philox_attn_keep_mask)
-from .fp8 import _LinearF8Fn, linear_fp8, ref_linear_fp8, ref_quant_e4m3  # noqa: F401
+from .fp8 import (  # noqa: F401
+    _LinearF8Fn, linear_fp8, linear_fp8_rows, ln_q8_ok, ref_linear_fp8, ref_linear_fp8_rows, ref_quant_e4m3,
+    ref_quant_e4m3_rows)
 from .gpt2 import (  # noqa: F401
     _LMHeadXentFn, _LM_CHUNK, _QKV_FUSED, _RES_EPI, _XENT_FUSED, _NT_GELU, _NT_DGELU, _NT_GD, add_layer_norm,
     attention, bias_gelu, cross_entropy, embedding, layer_norm, layer_norm_res, linear_add_layer_norm, lm_head_xent, mlp, mlp_add_layer_norm,
@@ -37,7 +40,8 @@ __all__ = [
     "ctr_lookup", "ctr_sparse_step", "ref_ctr_lookup", "ref_ctr_sparse_step",
     "layer_norm", "layer_norm_res", "add_layer_norm", "bias_gelu", "attention", "cross_entropy",
     "embedding", "ref_layer_norm", "ref_bias_gelu", "ref_attention",
-    "ref_cross_entropy", "use_hip", "linear", "linear_fp8", "ref_linear_fp8", "ref_quant_e4m3", "mlp", "qkv_attention", "lm_head_xent",
+    "ref_cross_entropy", "use_hip", "linear", "linear_fp8", "ref_linear_fp8", "ref_quant_e4m3", "ref_quant_e4m3_rows",
+    "linear_fp8_rows", "ref_linear_fp8_rows", "ln_q8_ok", "mlp", "qkv_attention", "lm_head_xent",
     "conv_bn_act", "conv_bn_ds_act", "bn_act", "deferred_reductions",
     "deferred_weight_grads", "flush_weight_grads",
     "Dropout", "dropout_spec", "philox_keep_mask", "attn_dropout_spec", "philox_attn_keep_mask", "ATTN_SITE0",

@@ -12,6 +12,19 @@ m·2^a, m ∈ [1, 2)): s = 2^e with e = 8 − a for m ≤ 1.75, else 7 − a, so
 amax·s ∈ (224, 448] (448 = e4m3's largest finite value); amax = 0 → e = 0;
 |e| ≤ 126 keeps s and 1/s normal.  q = RNE_e4m3(x·s); the GEMM multiplies the
 fp32 sums by 2^−e of both operands.
+
+Two forms of the activation operand:
+
+* per tensor, just in time (``linear_fp8``, ``GPT2Config.fp8 = "qkv"``): an amax
+  pass and a convert pass over x in front of the GEMM;
+* per token, from the producer (``linear_fp8_rows``, ``GPT2Config.fp8 = "ln"``):
+  the LayerNorm that computes x also writes each row as e4m3 under the row's
+  own scale — the rule above with amax taken over one row of the bf16-rounded
+  output (``ref_quant_e4m3_rows``) — and hands (q, 2^−e per row) to the GEMM,
+  which multiplies each output row by its token's scale in the epilogue.  No
+  pass over x, at least as fine a scale, still no state.
+
+The weight is quantised per tensor, per call, in both.
 """
 from __future__ import annotations
 
@@ -86,3 +99,81 @@ def linear_fp8(x, w, b=None):
     if use_hip(x) and not _f8_ok(x, w, b):
         return linear(x, w, b)
     return _LinearF8Fn.apply(x, w, b)
+
+
+# ----------------------------------------------------------------------------
+# per-token scales: the A operand as e4m3 rows written by the producing LayerNorm
+# (``GPT2Config.fp8 = "ln"``; csrc/hip/layernorm.hip Q8, gemm_nt_f8's row form)
+# ----------------------------------------------------------------------------
+
+def ref_quant_e4m3_rows(y: torch.Tensor):
+    """``ref_quant_e4m3`` applied to each row of y [..., C] on its own, in plain torch on the CPU:
+    (e4m3 bytes [rows, C], 2^−e per row as float32 [rows])."""
+    yf = y.detach().float().cpu().reshape(-1, y.shape[-1])
+    bits = yf.abs().amax(dim=1).view(torch.int32) & 0x7FFFFFFF
+    e = torch.where((bits & 0x7FFFFF) <= 0x600000, 8, 7) - ((bits >> 23) - 127)
+    e = torch.where(bits == 0, 0, e.clamp(-126, 126))
+    one = torch.ones(e.shape, dtype=torch.float32)
+    q = (yf * torch.ldexp(one, e).unsqueeze(1)).to(torch.float8_e4m3fn).view(torch.uint8)
+    return q.to(y.device), torch.ldexp(one, -e).to(y.device)
+
+
+def ln_q8_ok(h: torch.Tensor, *weights) -> bool:
+    """Whether the LayerNorm that produces h [..., C] should also write e4m3 rows for the products h·Wᵀ of
+    ``weights``: each within gemm_nt_f8's contract on the HIP path; always off it (the plain-torch reference)."""
+    if not use_hip(h):
+        return True
+    T = h.numel() // h.shape[-1]
+    m = _native.require_hip()
+    return h.dtype == torch.bfloat16 and all(
+        w.dtype == torch.bfloat16 and w.dim() == 2 and w.is_contiguous() and w.shape[1] == h.shape[-1]
+        and m.gemm_nt_f8_supported(T, w.shape[0], w.shape[1]) for w in weights)
+
+
+def _rows_ok(q, d, w, b=None) -> bool:
+    return (q is not None and q.is_cuda and w.dtype == torch.bfloat16 and w.dim() == 2 and w.is_contiguous()
+            and (b is None or b.dtype == torch.bfloat16) and q.shape[-1] == w.shape[1] and d.numel() == q.shape[0]
+            and _native.require_hip().gemm_nt_f8_supported(q.shape[0], w.shape[0], w.shape[1]))
+
+
+def _fwd_gemm_f8_rows(q, d, w, b=None):
+    """[rows, N] = (q·Wᵀ)·d[row]·dw (+ b): q, d the LayerNorm's rows and per-token scales, W quantised per
+    tensor just in time as ``_fwd_gemm_f8`` does; the caller has checked ``_rows_ok``."""
+    m = _native.require_hip()
+    qw, dw = m.quant_e4m3(w)
+    return m.gemm_nt_f8(q, d, qw, dw, b)
+
+
+def ref_linear_fp8_rows(q, d, w, b=None, dtype=torch.bfloat16):
+    """The per-token-scaled e4m3 product in plain torch: dequantised rows · dequantised W in fp32 (+ b), one rounding."""
+    a = q.cpu().view(torch.float8_e4m3fn).float() * d.cpu().float().unsqueeze(1)
+    y = a @ _dequant(*ref_quant_e4m3(w)).t()
+    if b is not None:
+        y = y + b.detach().float().cpu()
+    return y.to(dtype).to(q.device)
+
+
+class _LinearF8RowsFn(_LinearFn):
+    """``_LinearFn`` whose forward product takes x as the e4m3 rows (q, d) its LayerNorm wrote; saves the bf16
+    x and W, and the backward is ``_LinearFn``'s."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, q, d):
+        ctx.save_for_backward(x, w)
+        ctx.has_b = b is not None
+        ctx.b = b
+        if use_hip(x):
+            return _fwd_gemm_f8_rows(q, d, w, b).view(*x.shape[:-1], w.shape[0])
+        return ref_linear_fp8_rows(q, d, w, b, x.dtype).view(*x.shape[:-1], w.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _LinearFn.backward(ctx, dy) + (None, None)
+
+
+def linear_fp8_rows(x, f8, w, b=None):
+    """y = x·Wᵀ (+ b) with the forward product on ``f8`` = (q, d), x's e4m3 rows and per-token scales, and
+    ``ops.linear``'s bf16 backward; ``ops.linear`` itself where the e4m3 GEMM does not take the shape."""
+    if use_hip(x) and not _rows_ok(f8[0], f8[1], w, b):
+        return linear(x, w, b)
+    return _LinearF8RowsFn.apply(x, w, b, f8[0], f8[1])
