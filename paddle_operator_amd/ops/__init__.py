@@ -22,7 +22,7 @@ from .core import (  # noqa: F401
     ATTN_SITE0, attn_dropout_spec, attn_dropout_thr, philox_attn_keep_mask)
 from .fp8 import (  # noqa: F401
     _LinearF8Fn, linear_fp8, linear_fp8_rows, ln_q8_ok, ref_linear_fp8, ref_linear_fp8_rows, ref_quant_e4m3,
-    ref_quant_e4m3_rows)
+    ref_quant_e4m3_rows, ref_quant_mx8_rows, ref_linear_mx8_rows)
 from .gpt2 import (  # noqa: F401
     _LMHeadXentFn, _LM_CHUNK, _QKV_FUSED, _RES_EPI, _XENT_FUSED, _NT_GELU, _NT_DGELU, _NT_GD, add_layer_norm,
     attention, bias_gelu, cross_entropy, embedding, layer_norm, layer_norm_res, linear_add_layer_norm, lm_head_xent, mlp, mlp_add_layer_norm,
@@ -41,7 +41,8 @@ __all__ = [
     "layer_norm", "layer_norm_res", "add_layer_norm", "bias_gelu", "attention", "cross_entropy",
     "embedding", "ref_layer_norm", "ref_bias_gelu", "ref_attention",
     "ref_cross_entropy", "use_hip", "linear", "linear_fp8", "ref_linear_fp8", "ref_quant_e4m3", "ref_quant_e4m3_rows",
-    "linear_fp8_rows", "ref_linear_fp8_rows", "ln_q8_ok", "mlp", "qkv_attention", "lm_head_xent",
+    "linear_fp8_rows", "ref_linear_fp8_rows", "ln_q8_ok", "ref_quant_mx8_rows", "ref_linear_mx8_rows",
+    "mlp", "qkv_attention", "lm_head_xent",
     "conv_bn_act", "conv_bn_ds_act", "bn_act", "deferred_reductions",
     "deferred_weight_grads", "flush_weight_grads",
     "Dropout", "dropout_spec", "philox_keep_mask", "attn_dropout_spec", "philox_attn_keep_mask", "ATTN_SITE0",

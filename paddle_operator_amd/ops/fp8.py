@@ -24,7 +24,15 @@ Two forms of the activation operand:
   which multiplies each output row by its token's scale in the epilogue.  No
   pass over x, at least as fine a scale, still no state.
 
-The weight is quantised per tensor, per call, in both.
+A third form, for an operand whose producer never sees a whole row:
+
+* per (token, 32 columns): rows as MXFP8 — e4m3 bytes and one E8M0 scale byte per 32 consecutive columns, the rule
+  above with amax taken over the block of the bf16-rounded values (``ref_quant_mx8_rows``; not the OCP floor rule,
+  which lets amax·2^e reach 512 and saturates); the byte is 127 − e, the E8M0 code of 2^−e, the form gfx950's
+  scaled MFMA takes per 32 k (``ref_linear_mx8_rows``).  **Reference functions only**: no kernel writes or reads
+  such rows yet, and no ``GPT2Config.fp8`` value uses them; they state what fc2 on FP8 is to compute.
+
+The weight is quantised per tensor, per call, in all three.
 """
 from __future__ import annotations
 
@@ -177,3 +185,32 @@ def linear_fp8_rows(x, f8, w, b=None):
     if use_hip(x) and not _rows_ok(f8[0], f8[1], w, b):
         return linear(x, w, b)
     return _LinearF8RowsFn.apply(x, w, b, f8[0], f8[1])
+
+
+# ----------------------------------------------------------------------------
+# MXFP8 rows: one E8M0 scale per (token, 32 columns); the reference semantics only, no kernel uses them yet
+# ----------------------------------------------------------------------------
+
+def ref_quant_mx8_rows(y: torch.Tensor):
+    """``ref_quant_e4m3`` applied to each block of 32 consecutive columns of each row of y [..., K], K % 32 = 0, in
+    plain torch on the CPU: (e4m3 bytes uint8 [rows, K], E8M0 scale bytes uint8 [rows, K / 32] = 127 − e)."""
+    K = y.shape[-1]
+    yf = y.detach().float().cpu().reshape(-1, K // 32, 32)
+    bits = yf.abs().amax(dim=2).view(torch.int32) & 0x7FFFFFFF
+    e = torch.where((bits & 0x7FFFFF) <= 0x600000, 8, 7) - ((bits >> 23) - 127)
+    e = torch.where(bits == 0, 0, e.clamp(-126, 126))
+    q = (yf * torch.ldexp(torch.ones(e.shape), e).unsqueeze(2)).to(torch.float8_e4m3fn).view(torch.uint8)
+    return q.reshape(-1, K).to(y.device), (127 - e).to(torch.uint8).to(y.device)
+
+
+def ref_linear_mx8_rows(q, s, w, b=None, res=None, dtype=torch.bfloat16):
+    """The MXFP8 product in plain torch: rows dequantised block by block (q·2^(s − 127)) · dequantised W in fp32
+    (+ b) (+ res), one rounding.  W is quantised per tensor (``ref_quant_e4m3``)."""
+    d = torch.ldexp(torch.ones(s.shape), s.cpu().to(torch.int32) - 127)
+    a = q.cpu().view(torch.float8_e4m3fn).float() * d.repeat_interleave(32, dim=1)
+    y = a @ _dequant(*ref_quant_e4m3(w)).t()
+    if b is not None:
+        y = y + b.detach().float().cpu()
+    if res is not None:
+        y = y + res.detach().float().cpu().reshape(y.shape)
+    return y.to(dtype).to(q.device)
