@@ -685,9 +685,10 @@ bool gemm_nt_f8_supported(int64_t M, int64_t N, int64_t K) {
 
 // c = bf16((qa·qbᵀ)·da·db (+ bias)): qa [M, K], qb [N, K] e4m3 bytes (dense rows, any row stride the kernel takes);
 // da one float, or M floats = one scale per row of qa (the per-token scales a LayerNorm wrote).
-// gelu (the row form only): (gelu', gelu) of the fp32 (qa·qbᵀ)·da[m]·db + bias, as gemm_nt_gelu(saved_grad=true)
+// gelu (the row form only): (gelu', gelu) of the fp32 (qa·qbᵀ)·da[m]·db + bias, as gemm_nt_gelu(saved_grad=true);
+// mx (with gelu): and gelu's rows as MXFP8, (q [M, N], s [M, N / 32]) uint8 as ops.ref_quant_mx8_rows(gelu) gives them
 static std::vector<at::Tensor> f8_run(const char* what, at::Tensor qa, at::Tensor da, at::Tensor qb, at::Tensor db,
-                                      c10::optional<at::Tensor> bias, bool gelu) {
+                                      c10::optional<at::Tensor> bias, bool gelu, bool mx = false) {
   int64_t M, K, lda, N, Kb, ldb;
   rows_view(qa, what, M, K, lda);
   rows_view(qb, what, N, Kb, ldb);
@@ -709,11 +710,18 @@ static std::vector<at::Tensor> f8_run(const char* what, at::Tensor qa, at::Tenso
   at::Tensor c = at::empty({M, N}, qa.options().dtype(at::kBFloat16));
   at::Tensor y;
   if (gelu) y = at::empty({M, N}, c.options());
+  at::Tensor q, s;
+  if (mx) {
+    TORCH_CHECK(gelu && N % 128 == 0, what, ": MXFP8 rows come with the GELU epilogue, N % 128 = 0");
+    q = at::empty({M, N}, qa.options());
+    s = at::empty({M, N / 32}, qa.options());
+  }
   const int epi = gelu ? pdo::EPI_GELU_SAVE_GRAD : bptr ? pdo::EPI_BIAS : pdo::EPI_PLAIN;
   const int rc = pdo::gemm_nt_f8(qa.data_ptr<uint8_t>(), fp(da), qb.data_ptr<uint8_t>(), fp(db), (int)M, (int)N, (int)K,
                                  (int)lda, (int)ldb, bp(c), (int)N, epi, bptr, cur_stream(), rows, gelu ? bp(y) : nullptr,
-                                 (int)N);
+                                 (int)N, mx ? q.data_ptr<uint8_t>() : nullptr, mx ? s.data_ptr<uint8_t>() : nullptr);
   TORCH_CHECK(rc == 0, what, " rejected the shape (code ", rc, ")");
+  if (mx) return {c, y, q, s};
   if (gelu) return {c, y};
   return {c};
 }
@@ -722,8 +730,45 @@ at::Tensor gemm_nt_f8(at::Tensor qa, at::Tensor da, at::Tensor qb, at::Tensor db
   return f8_run("gemm_nt_f8", qa, da, qb, db, bias, false)[0];
 }
 
-std::vector<at::Tensor> gemm_nt_f8_gelu(at::Tensor qa, at::Tensor da, at::Tensor qb, at::Tensor db, at::Tensor bias) {
-  return f8_run("gemm_nt_f8_gelu", qa, da, qb, db, bias, true);
+std::vector<at::Tensor> gemm_nt_f8_gelu(at::Tensor qa, at::Tensor da, at::Tensor qb, at::Tensor db, at::Tensor bias,
+                                        bool mx) {
+  return f8_run("gemm_nt_f8_gelu", qa, da, qb, db, bias, true, mx);
+}
+
+bool gemm_nt_mx8_supported(int64_t M, int64_t N, int64_t K) { return gemm_nt_f8_supported(M, N, K); }
+
+// c = bf16(Σ_k (q·2^(s − 127))·qb · db (+ bias) (+ res)): q [M, K] e4m3 bytes and s [M, K / 32] E8M0 bytes, the MXFP8
+// rows gemm_nt_f8_gelu(mx=true) writes (contiguous); qb [N, K] e4m3 bytes with db one float; res [M, N] contiguous
+// bf16 (needs bias: the residual epilogue is bias + res)
+at::Tensor gemm_nt_mx8(at::Tensor q, at::Tensor s, at::Tensor qb, at::Tensor db, c10::optional<at::Tensor> bias,
+                       c10::optional<at::Tensor> res) {
+  const char* what = "gemm_nt_mx8";
+  CHECK_IN(q); CHECK_IN(s); CHECK_IN(qb); CHECK_IN(db); CHECK_F32(db);
+  TORCH_CHECK(q.scalar_type() == at::kByte && s.scalar_type() == at::kByte && qb.scalar_type() == at::kByte &&
+                  q.dim() == 2 && s.dim() == 2 && qb.dim() == 2 && q.size(1) == qb.size(1) && q.size(1) % 32 == 0 &&
+                  s.size(0) == q.size(0) && s.size(1) == q.size(1) / 32 && db.numel() == 1,
+              what, ": q [M, K], s [M, K / 32], qb [N, K] uint8, db one float");
+  const int64_t M = q.size(0), K = q.size(1), N = qb.size(0);
+  TORCH_CHECK(gemm_nt_mx8_supported(M, N, K), what, " rejected the shape (code -2)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(qb.data_ptr()) % 16 == 0,
+              what, ": operands must be 16-byte aligned");
+  const bf16* bptr = nullptr;
+  const bf16* rptr = nullptr;
+  if (bias.has_value()) {
+    CHECK_IN((*bias)); CHECK_BF16((*bias)); TORCH_CHECK(bias->numel() == N);
+    bptr = bp(*bias);
+  }
+  if (res.has_value()) {
+    CHECK_IN((*res)); CHECK_BF16((*res));
+    TORCH_CHECK(bptr && res->dim() == 2 && res->size(0) == M && res->size(1) == N, what, ": res [M, N] comes with a bias");
+    rptr = bp(*res);
+  }
+  at::Tensor c = at::empty({M, N}, q.options().dtype(at::kBFloat16));
+  const int epi = rptr ? pdo::EPI_BIAS_ADD : bptr ? pdo::EPI_BIAS : pdo::EPI_PLAIN;
+  const int rc = pdo::gemm_nt_mx8(q.data_ptr<uint8_t>(), s.data_ptr<uint8_t>(), qb.data_ptr<uint8_t>(), fp(db), (int)M,
+                                  (int)N, (int)K, (int)K, (int)K, bp(c), (int)N, epi, bptr, rptr, (int)N, cur_stream());
+  TORCH_CHECK(rc == 0, what, " rejected the arguments (code ", rc, ")");
+  return c;
 }
 
 // c = a·bᵀ (+ bias) + r (r: [M, N] contiguous bf16), one pass; one rounding on the 4-wave mainloop
@@ -1886,7 +1931,11 @@ PYBIND11_MODULE(_pdo_hip, m) {
   m.def("quant_e4m3", &quant_e4m3, py::arg("x"));
   m.def("gemm_nt_f8_supported", &gemm_nt_f8_supported);
   m.def("gemm_nt_f8", &gemm_nt_f8, py::arg("qa"), py::arg("da"), py::arg("qb"), py::arg("db"), py::arg("bias") = py::none());
-  m.def("gemm_nt_f8_gelu", &gemm_nt_f8_gelu, py::arg("qa"), py::arg("da"), py::arg("qb"), py::arg("db"), py::arg("bias"));
+  m.def("gemm_nt_f8_gelu", &gemm_nt_f8_gelu, py::arg("qa"), py::arg("da"), py::arg("qb"), py::arg("db"), py::arg("bias"),
+        py::arg("mx") = false);
+  m.def("gemm_nt_mx8_supported", &gemm_nt_mx8_supported);
+  m.def("gemm_nt_mx8", &gemm_nt_mx8, py::arg("q"), py::arg("s"), py::arg("qb"), py::arg("db"), py::arg("bias") = py::none(),
+        py::arg("res") = py::none());
   m.def("gemm_nt_gelu", &gemm_nt_gelu, py::arg("a"), py::arg("b"), py::arg("bias"), py::arg("saved_grad") = false);
   m.def("gemm_nt_dgelu", &gemm_nt_dgelu, py::arg("a"), py::arg("b"), py::arg("pre"), py::arg("bias"),
         py::arg("db_out") = py::none(), py::arg("saved_grad") = false);

@@ -14,6 +14,14 @@
 // fc1's epilogue EPI_GELU_SAVE_GRAD, as gemm_nt4 stores it: x = fma(acc, da[m]·db,
 // bias), C = bf16(gelu'(x)), Y = bf16(gelu(x)) (common.h, gelu_and_grad2).
 //
+// MX (gemm_nt_f8_kernel<EPI_GELU_SAVE_GRAD, true, true>): that epilogue also writes the bf16-rounded Y as MXFP8
+// rows for gemm_nt_mx8 (fc2): Q[M][N] e4m3 bytes and S[M][N / 32] E8M0 bytes 127 − e, both dense row-major, e by
+// quant_f8.hip's rule over each block of 32 consecutive columns (f8_quant.h).  Per (i, e) a lane holds 8
+// consecutive columns of one row, so a block is a quad of lanes: amax on the |bits| of the bf16 values with two
+// DPP quad_perm steps, one multiply and f8_cvt8, an 8-B non-temporal store per lane and row.  A wave's 128
+// columns are four blocks: their bytes are gathered into one dword by two DPP row rotations and stored by one
+// lane per row (N % 128 = 0: 4-B aligned).  The other instantiations' code does not change.
+//
 // Work split: gemm_nt4's — 256 × 256 output tile, 4 waves, one per SIMD, each
 // owning a 128 × 128 block as 64 16×16 accumulators pinned to the accumulator
 // file; persistent one-workgroup-per-CU grid with the XCD remap and the grouped
@@ -58,6 +66,7 @@
 #include <utility>
 
 #include "cdna4.h"
+#include "f8_quant.h"
 #include "gemm_nt_epi.h"
 #include "kernels.h"
 
@@ -92,17 +101,23 @@ struct RowsOut {  // of the row form: EPI_GELU_SAVE_GRAD's second output
   bf16* Y;
   int ldy;
 };
+struct MxOut : RowsOut {  // MX: Y's rows once more as MXFP8, dense: Q[M][N] e4m3 bytes, S[M][N / 32] E8M0 bytes
+  unsigned char* Q;
+  unsigned char* S;
+};
 
 // ROWS = false: da is one float; true: M floats, one per row of A (per token)
-template <int EPI, bool ROWS = false>
+// MX (fc1's epilogue on the row form only): also write bf16(Y) as MXFP8 rows for gemm_nt_mx8
+template <int EPI, bool ROWS = false, bool MX = false>
 __global__ __launch_bounds__(NTHR, 1) void gemm_nt_f8_kernel(const unsigned char* __restrict__ A,
                                                              const unsigned char* __restrict__ B, int lda, int ldb,
                                                              int M, int N, int nk, bf16* __restrict__ C, int ldc,
                                                              const bf16* __restrict__ bias,
                                                              const float* __restrict__ da,
                                                              const float* __restrict__ db, int group_m,
-                                                             std::conditional_t<ROWS, RowsOut, NoOut> yo) {
+                                                             std::conditional_t<MX, MxOut, std::conditional_t<ROWS, RowsOut, NoOut>> yo) {
   static_assert(epi_f8(EPI, ROWS), "no such epilogue");
+  static_assert(!MX || (ROWS && EPI == EPI_GELU_SAVE_GRAD), "MXFP8 rows come from fc1's epilogue");
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 2 * OPB];  // [buf][A|B][256][128]
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -266,7 +281,28 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_nt_f8_kernel(const unsigned char
             g[q + 1] = gg[1];
           }
           __builtin_nontemporal_store(to_bf16(g), reinterpret_cast<bf16x8*>(crow));
-          __builtin_nontemporal_store(to_bf16(y), reinterpret_cast<bf16x8*>(yo.Y + (mr + 16 * i + e) * yo.ldy + nb));
+          const bf16x8 yb = to_bf16(y);
+          __builtin_nontemporal_store(yb, reinterpret_cast<bf16x8*>(yo.Y + (mr + 16 * i + e) * yo.ldy + nb));
+          if constexpr (MX) {
+            // the 32-column block of this row is the quad of lanes around this one: amax on the |bits| of the
+            // bf16-rounded values (an integer max orders them as floats), two quad_perm steps
+            const u16x8 ub = __builtin_bit_cast(u16x8, yb) & (unsigned short)0x7fff;
+            int am = max(max(max((int)ub[0], (int)ub[1]), max((int)ub[2], (int)ub[3])),
+                         max(max((int)ub[4], (int)ub[5]), max((int)ub[6], (int)ub[7])));
+            am = max(am, __builtin_amdgcn_mov_dpp(am, 0xb1, 0xf, 0xf, false));  // quad_perm:[1,0,3,2]
+            am = max(am, __builtin_amdgcn_mov_dpp(am, 0x4e, 0xf, 0xf, false));  // quad_perm:[2,3,0,1]
+            const int ex = f8_scale_exp((unsigned)am << 16);
+            const float sx = f8_pow2(ex);
+            const size_t row = mr + 16 * i + e;
+            const i32x2 qv = f8_cvt8(to_f32(yb) * f32x8{sx, sx, sx, sx, sx, sx, sx, sx});
+            __builtin_nontemporal_store(qv, reinterpret_cast<i32x2*>(yo.Q + row * (size_t)N + nb));
+            // the wave's four scale bytes of this row (127 − e, block b in byte b) gathered by two rotations of the
+            // 16-lane row — an OR over lanes l, l ± 4, l ± 8, l ± 12 whichever way it turns — and stored as one dword
+            int sw4 = (127 - ex) << (8 * ((lane >> 2) & 3));
+            sw4 |= __builtin_amdgcn_mov_dpp(sw4, 0x124, 0xf, 0xf, false);  // row_ror:4
+            sw4 |= __builtin_amdgcn_mov_dpp(sw4, 0x128, 0xf, 0xf, false);  // row_ror:8
+            if ((lane & 15) == 0) *reinterpret_cast<int*>(yo.S + row * (size_t)(N >> 5) + ((n0 + wn * 128) >> 5)) = sw4;
+          }
         } else {
           __builtin_nontemporal_store(to_bf16(x), reinterpret_cast<bf16x8*>(crow));
         }
@@ -325,7 +361,7 @@ int gemm_nt_f8_ok(int M, int N, int K, int lda, int ldb, int ldc) {
 
 int gemm_nt_f8(const unsigned char* A, const float* da, const unsigned char* B, const float* db, int M, int N, int K,
                int lda, int ldb, bf16* C, int ldc, int epi, const bf16* bias, hipStream_t st, bool da_rows, bf16* Y,
-               int ldy) {
+               int ldy, unsigned char* Q, unsigned char* S) {
   if (!gemm_nt_f8_ok(M, N, K, lda, ldb, ldc)) return -2;
   if (!da || !db || (da_rows && reinterpret_cast<uintptr_t>(da) % 16)) return -3;
   // gemm_nt()'s verdict on the epilogue's own arguments (bias, Y, ldy); the 4-wave-only fc1 epilogue exists here
@@ -336,6 +372,13 @@ int gemm_nt_f8(const unsigned char* A, const float* da, const unsigned char* B, 
   if (tiles > 0x7fffffffLL) return -2;
   constexpr int group_m = 4;  // gemm_nt4's
   const int g = persistent_grid(tiles);
+  if (Q || S) {  // fc1's epilogue with the MXFP8 copy of Y
+    if (!da_rows || epi != EPI_GELU_SAVE_GRAD) return -4;
+    if (!Q || !S || reinterpret_cast<uintptr_t>(Q) % 8 || reinterpret_cast<uintptr_t>(S) % 4) return -3;
+    gemm_nt_f8_kernel<EPI_GELU_SAVE_GRAD, true, true><<<g, NTHR, 0, st>>>(A, B, lda, ldb, M, N, K / BK, C, ldc, bias, da,
+                                                                          db, group_m, MxOut{{Y, ldy}, Q, S});
+    return 0;
+  }
   if (da_rows)
     return nt_epi_dispatch(std::integer_sequence<int, EPI_PLAIN, EPI_BIAS, EPI_GELU_SAVE_GRAD>{}, epi, [&](auto e) {
       gemm_nt_f8_kernel<decltype(e)::value, true><<<g, NTHR, 0, st>>>(A, B, lda, ldb, M, N, K / BK, C, ldc, bias, da, db,

@@ -243,7 +243,17 @@ int quant_e4m3(const bf16* x, long long rows, long long cols, long long ld, cons
 int gemm_nt_f8_ok(int M, int N, int K, int lda, int ldb, int ldc);
 int gemm_nt_f8(const unsigned char* A, const float* da, const unsigned char* B, const float* db, int M, int N, int K,
                int lda, int ldb, bf16* C, int ldc, int epi, const bf16* bias, hipStream_t st, bool da_rows = false,
-               bf16* Y = nullptr, int ldy = 0);
+               bf16* Y = nullptr, int ldy = 0, unsigned char* Q = nullptr, unsigned char* S = nullptr);
+// Q, S (both or neither; da_rows with EPI_GELU_SAVE_GRAD only, else -4): the same launch also writes bf16(Y) as MXFP8
+// rows, dense: Q[M][N] e4m3 bytes (8-B aligned), S[M][N / 32] E8M0 bytes 127 − e (4-B aligned), e by quant_e4m3's rule
+// over each block of 32 consecutive columns of the bf16-rounded Y.
+// gemm_nt_mx8.hip: C[M][N] = bf16(Σ_k (A[m][k]·2^(S[m][k / 32] − 127))·B[n][k]·db (+ bias[N]) (+ res[M][N])), A such
+// MXFP8 rows (S dense, row stride K / 32), B per-tensor e4m3 bytes with its device float db; fp32 accumulation, one
+// rounding.  gemm_nt_f8_ok's shape rules (-2).  epi: EPI_PLAIN, EPI_BIAS, or EPI_BIAS_ADD (x = fma(acc, db, bias) +
+// res; res, ldr as gemm_nt_args_rc asks of Y: ldr % 4 = 0 and ≥ N, else -3); any other value -4.
+int gemm_nt_mx8(const unsigned char* A, const unsigned char* S, const unsigned char* B, const float* db, int M, int N,
+                int K, int lda, int ldb, bf16* C, int ldc, int epi, const bf16* bias, const bf16* res, int ldr,
+                hipStream_t st);
 // transpose.hip: out[C][R] = in[R][C], R and C multiples of 64
 int transpose_bf16(const bf16* in, bf16* out, int R, int C, hipStream_t st);
 // every matrix of a table in one launch: table = n × {first tile, src offset, dst

@@ -48,10 +48,11 @@ def parse_args(argv=None):
                     help="gpt2: attention-probability dropout inside the flash-attention kernels (quantised to 1/256; "
                          "default 0)")
     ap.add_argument("--dropout-seed", type=int, default=0, help="gpt2: seed of the dropout masks")
-    ap.add_argument("--fp8", default=None, choices=["off", "qkv", "ln"],
+    ap.add_argument("--fp8", default=None, choices=["off", "qkv", "ln", "lnmx"],
                     help="gpt2: forward products on FP8 (e4m3) operands with bf16 gradients; qkv = the QKV projection, "
                          "quantised per tensor just in time; ln = QKV and fc1 from e4m3 rows the LayerNorms write, one "
-                         "scale per token (default off)")
+                         "scale per token; lnmx = ln, and fc2 from MXFP8 rows fc1's GELU epilogue writes, one E8M0 scale "
+                         "per token and 32 columns (default off)")
     ap.add_argument("--data", default=os.environ.get("PDO_TRAIN_DATA", ""),
                     help="gpt2: training token file, raw little-endian uint16 ids (nanoGPT train.bin); resnet50: "
                          "directory with images.npy (uint8 [n, R, R, 3]) and labels.npy ([n]); wide_deep / deepfm "

@@ -55,15 +55,16 @@ class GPT2Config:
     attn_pdrop: float = 0.0
     # forward products on FP8 (e4m3) operands, gradients stay bf16: "off" | "qkv" (the QKV projection, quantised
     # per tensor just in time, ops.linear_fp8) | "ln" (QKV and fc1 from e4m3 rows that the producing LayerNorm
-    # writes with one scale per token, ops.linear_fp8_rows)
+    # writes with one scale per token, ops.linear_fp8_rows) | "lnmx" ("ln", and fc2 from MXFP8 rows that fc1's GELU
+    # epilogue writes with one E8M0 scale per token and 32 columns, csrc/hip/gemm_nt_mx8.hip)
     fp8: str = "off"
     # 128: 50304 rows.  256 (PDO_PAD_VOCAB=256): 50432, full 256-wide tiles, so the
     # LM head's forward / dX GEMMs enter gemm_nt4 and its dW gemm_dw4's full-height tiles
     pad_vocab_to: int = field(default_factory=lambda: int(os.environ.get("PDO_PAD_VOCAB", "128")))
 
     def __post_init__(self):
-        if self.fp8 not in ("off", "qkv", "ln"):
-            raise ValueError(f"GPT2Config.fp8 must be 'off', 'qkv' or 'ln', got {self.fp8!r}")
+        if self.fp8 not in ("off", "qkv", "ln", "lnmx"):
+            raise ValueError(f"GPT2Config.fp8 must be 'off', 'qkv', 'ln' or 'lnmx', got {self.fp8!r}")
 
     @property
     def padded_vocab(self) -> int:
@@ -141,7 +142,7 @@ class Block(nn.Module):
         ops.linear_add_layer_norm / ops.mlp_add_layer_norm) and the following
         LayerNorm reads the stream once.
 
-        ``f8`` (fp8 = "ln"): h as e4m3 rows with per-token scales, written by the
+        ``f8`` (fp8 = "ln" / "lnmx"): h as e4m3 rows with per-token scales, written by the
         LayerNorm that produced it; LN2 then writes h2's rows for fc1, and with
         ``q8_next`` the result gains LN_next's rows for the next block:
         (x_out, LN_next(x_out), (q, d)).
@@ -153,7 +154,7 @@ class Block(nn.Module):
                                                  cfg.ln_eps, drop_attn, q8=f8 is not None)
         return ops.mlp_add_layer_norm(h2, self.fc.weight, self.fc.bias, self.fc_proj.weight, self.fc_proj.bias,
                                       x, ln_next_w, ln_next_b, cfg.ln_eps, drop_mlp, f8=f8_2[0] if f8_2 else None,
-                                      q8=q8_next)
+                                      q8=q8_next, mx=cfg.fp8 == "lnmx")
 
 
 class GPT2(nn.Module):
@@ -213,9 +214,9 @@ class GPT2(nn.Module):
         d0 = self._drop(cfg.embd_pdrop, 0)
         x = ops.embedding(idx, self.wte, self.wpe, d0, masked_grad=True)
         blk0 = self.blocks[0]
-        # fp8 = "ln": every LayerNorm that feeds a block's QKV / fc1 also writes its rows as e4m3 (the final one,
+        # fp8 = "ln" / "lnmx": every LayerNorm that feeds a block's QKV / fc1 also writes its rows as e4m3 (the final one,
         # which feeds the LM head, does not); outside the FP8 GEMM's shape contract nothing is asked and bf16 runs
-        q8 = cfg.fp8 == "ln" and ops.ln_q8_ok(x, blk0.qkv.weight, blk0.fc.weight)
+        q8 = cfg.fp8 in ("ln", "lnmx") and ops.ln_q8_ok(x, blk0.qkv.weight, blk0.fc.weight)
         x, h, *f8 = ops.layer_norm_res(x, blk0.ln1_w, blk0.ln1_b, cfg.ln_eps, d0, q8=q8)
         for i, blk in enumerate(self.blocks):
             da, dm = self._drop(cfg.resid_pdrop, 1 + 2 * i), self._drop(cfg.resid_pdrop, 2 + 2 * i)

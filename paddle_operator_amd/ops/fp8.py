@@ -1,5 +1,5 @@
 """FP8 (OCP e4m3) forward products: per-tensor power-of-two quantisation and
-the e4m3 GEMM (csrc/hip/quant_f8.hip, csrc/hip/gemm_nt_f8.hip).
+the e4m3 GEMMs (csrc/hip/quant_f8.hip, csrc/hip/gemm_nt_f8.hip, csrc/hip/gemm_nt_mx8.hip).
 
 Straight-through FP8 forward training: only the forward product y = x·Wᵀ (+ b)
 runs on e4m3 operands; the backward keeps the saved **bf16** x and W and is
@@ -29,8 +29,11 @@ A third form, for an operand whose producer never sees a whole row:
 * per (token, 32 columns): rows as MXFP8 — e4m3 bytes and one E8M0 scale byte per 32 consecutive columns, the rule
   above with amax taken over the block of the bf16-rounded values (``ref_quant_mx8_rows``; not the OCP floor rule,
   which lets amax·2^e reach 512 and saturates); the byte is 127 − e, the E8M0 code of 2^−e, the form gfx950's
-  scaled MFMA takes per 32 k (``ref_linear_mx8_rows``).  **Reference functions only**: no kernel writes or reads
-  such rows yet, and no ``GPT2Config.fp8`` value uses them; they state what fc2 on FP8 is to compute.
+  scaled MFMA takes per 32 k (``ref_linear_mx8_rows``).  This is fc2 under ``GPT2Config.fp8 = "lnmx"``: fc1's GELU
+  epilogue on gemm_nt_f8 writes its bf16 output once more as such rows (``gemm_nt_f8_gelu(mx=True)``, bit for bit
+  ``ref_quant_mx8_rows`` of the stored bf16), and ``gemm_nt_mx8`` multiplies them with the per-tensor e4m3 W2 on
+  the scaled MFMA, adding fc2's bias and the residual stream in its epilogue (``ops.mlp(mx=True)``,
+  ``ops.mlp_add_layer_norm(mx=True)``).  The bf16 output is still stored: the backward and fc2's dW read it.
 
 The weight is quantised per tensor, per call, in all three.
 """
@@ -188,7 +191,8 @@ def linear_fp8_rows(x, f8, w, b=None):
 
 
 # ----------------------------------------------------------------------------
-# MXFP8 rows: one E8M0 scale per (token, 32 columns); the reference semantics only, no kernel uses them yet
+# MXFP8 rows: one E8M0 scale per (token, 32 columns), written by fc1's epilogue and read by gemm_nt_mx8
+# (``GPT2Config.fp8 = "lnmx"``; csrc/hip/gemm_nt_f8.hip MX, csrc/hip/gemm_nt_mx8.hip)
 # ----------------------------------------------------------------------------
 
 def ref_quant_mx8_rows(y: torch.Tensor):
@@ -214,3 +218,21 @@ def ref_linear_mx8_rows(q, s, w, b=None, res=None, dtype=torch.bfloat16):
     if res is not None:
         y = y + res.detach().float().cpu().reshape(y.shape)
     return y.to(dtype).to(q.device)
+
+
+def _mx_ok(T, w, b=None, res=None) -> bool:
+    """Whether gemm_nt_mx8 takes [T, K] MXFP8 rows · Wᵀ (+ b + res): W bf16 contiguous [N, K] within the kernel's
+    shape contract, res (which comes with b) bf16 contiguous of T·N elements."""
+    return (w.is_cuda and w.dtype == torch.bfloat16 and w.dim() == 2 and w.is_contiguous()
+            and (b is None or b.dtype == torch.bfloat16)
+            and (res is None or (b is not None and res.dtype == torch.bfloat16 and res.is_contiguous()
+                                 and res.numel() == T * w.shape[0]))
+            and _native.require_hip().gemm_nt_mx8_supported(T, w.shape[0], w.shape[1]))
+
+
+def _fwd_gemm_mx8(q, s, w, b=None, res=None):
+    """[rows, N] = (q·2^(s − 127))·Wᵀ·dw (+ b) (+ res): q, s the MXFP8 rows fc1's epilogue wrote, W quantised per
+    tensor just in time as ``_fwd_gemm_f8_rows`` does; the caller has checked ``_mx_ok``."""
+    m = _native.require_hip()
+    qw, dw = m.quant_e4m3(w)
+    return m.gemm_nt_mx8(q, s, qw, dw, b, None if res is None else res.reshape(-1, w.shape[0]))

@@ -74,7 +74,7 @@ def hip_flags(name):
     # live in the accumulator file; the vgpr form made hipcc shuttle them
     # through arch VGPRs, 3 VALU per MFMA)
     vgpr_form = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
-    agpr_files = {"gemm_nt4.hip", "gemm_dw4.hip", "gemm_nt_f8.hip"}
+    agpr_files = {"gemm_nt4.hip", "gemm_dw4.hip", "gemm_nt_f8.hip", "gemm_nt_mx8.hip"}
     # per-file extras: attention's softmax max-reductions become v_max3 only
     # without NaN canonicalisation (scores are never NaN; ±inf masks keep working)
     # lars.hip: no packed fp32 instructions (v_pk_fma_f32 and kin) in its f32x4 arithmetic

@@ -12,8 +12,12 @@ e4m3 rows (q8), gemm_nt_f8 on per-token scales against the scalar form, fc1 (C â
 gemm_nt4's saved-gelu' epilogue, and the net per layer of each product = (LayerNorm q8 âˆ’ LayerNorm) + quantise W +
 FP8 GEMM âˆ’ bf16 GEMM.
 
-    python tools/f8_probe.py --step 64 [--model gpt2-medium] [--steps 8] [--rounds 3]   # step time, off / qkv / ln
-    python tools/f8_probe.py --losses 40 [--micro-batch 8]                              # losses of the three modes
+And what ``--fp8 lnmx`` adds (profiles/fp8_mx.md): fc1 on gemm_nt_f8_gelu with the MXFP8 copy of its output
+(f8_fc1_mx against f8_fc1), fc2 (4C â†’ C, bias + residual epilogue) on gemm_nt_mx8 against gemm_nt4, and the net per
+layer = (f8_fc1_mx âˆ’ f8_fc1) + quantise W2 + mx8_fc2 âˆ’ nt4_fc2.
+
+    python tools/f8_probe.py --step 64 [--model gpt2-medium] [--steps 8] [--rounds 3]   # step time, off / qkv / ln / lnmx
+    python tools/f8_probe.py --losses 40 [--micro-batch 8]                              # losses of the modes
 
 --step: one trainer, GPT2Config.fp8 switched between rounds (host clock around a device synchronise, warm-up for
 every mode).  --losses: a fresh trainer per mode, same seed, synthetic stream, lr 3e-4.
@@ -43,7 +47,7 @@ def bench(fn, iters, warm=3):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
-MODES = ("off", "qkv", "ln")
+MODES = ("off", "qkv", "ln", "lnmx")
 
 
 def _trainer(model, micro_batch, seq):
@@ -95,7 +99,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--widths", default="768,1024,1280")
     ap.add_argument("--step", type=int, default=0, metavar="MICRO_BATCH", help="time the training step instead")
-    ap.add_argument("--losses", type=int, default=0, metavar="STEPS", help="print the three modes' losses instead")
+    ap.add_argument("--losses", type=int, default=0, metavar="STEPS", help="print the modes' losses instead")
     ap.add_argument("--model", default="gpt2-medium")
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--seq", type=int, default=1024)
@@ -128,13 +132,20 @@ def main():
         w1 = torch.empty(4 * C, K, device=dev, dtype=torch.bfloat16).normal_(0, 0.02, generator=g)
         b1 = torch.empty(4 * C, device=dev, dtype=torch.bfloat16).uniform_(-0.1, 0.1, generator=g)
         qw1, dw1 = m.quant_e4m3(w1)
+        # --fp8 lnmx: fc2 from the MXFP8 rows of fc1's output, bias and residual (x) in the epilogue
+        w2 = torch.empty(C, 4 * C, device=dev, dtype=torch.bfloat16).normal_(0, 0.02, generator=g)
+        b2 = torch.empty(C, device=dev, dtype=torch.bfloat16).uniform_(-0.1, 0.1, generator=g)
+        _, h, qh, sh = m.gemm_nt_f8_gelu(qr, dr, qw1, dw1, b1, mx=True)
+        qw2, dw2 = m.quant_e4m3(w2)
 
         fns = {"f8_gemm": lambda: m.gemm_nt_f8(qx, dx, qw, dw, b), "quant_x": lambda: m.quant_e4m3(x),
                "quant_w": lambda: m.quant_e4m3(w), "f8_whole": whole, "nt4": lambda: m.gemm_nt(x, w, b),
                "ln": lambda: m.layernorm_fwd(x, lw, lb, 1e-5), "ln_q8": lambda: m.layernorm_fwd(x, lw, lb, 1e-5, True),
                "f8_rows": lambda: m.gemm_nt_f8(qr, dr, qw, dw, b), "quant_w1": lambda: m.quant_e4m3(w1),
                "f8_fc1": lambda: m.gemm_nt_f8_gelu(qr, dr, qw1, dw1, b1),
-               "nt4_fc1": lambda: m.gemm_nt_gelu(x, w1, b1, saved_grad=True)}
+               "nt4_fc1": lambda: m.gemm_nt_gelu(x, w1, b1, saved_grad=True),
+               "f8_fc1_mx": lambda: m.gemm_nt_f8_gelu(qr, dr, qw1, dw1, b1, mx=True), "quant_w2": lambda: m.quant_e4m3(w2),
+               "mx8_fc2": lambda: m.gemm_nt_mx8(qh, sh, qw2, dw2, b2, x), "nt4_fc2": lambda: m.gemm_nt_add(h, w2, x, bias=b2)}
         y8, y16 = whole().float(), m.gemm_nt(x, w, b).float()
         rel = ((y8 - y16).abs().max() / y16.pow(2).mean().sqrt()).item()
         del y8, y16
@@ -153,8 +164,11 @@ def main():
         ln_extra = rec["ln_q8_us"] - rec["ln_us"]  # paid once per LayerNorm, i.e. once per product
         rec["ln_net_qkv_us"] = round(ln_extra + rec["quant_w_us"] + rec["f8_rows_us"] - rec["nt4_us"], 1)
         rec["ln_net_fc1_us"] = round(ln_extra + rec["quant_w1_us"] + rec["f8_fc1_us"] - rec["nt4_fc1_us"], 1)
+        rec["mx8_fc2_PF"] = round(2.0 * M * C * 4 * C / rec["mx8_fc2_us"] / 1e9, 3)
+        rec["mx_net_fc2_us"] = round(rec["f8_fc1_mx_us"] - rec["f8_fc1_us"] + rec["quant_w2_us"] + rec["mx8_fc2_us"]
+                                     - rec["nt4_fc2_us"], 1)
         print(json.dumps(rec), flush=True)
-        del x, w, b, qx, qw, qr, dr, w1, b1, qw1
+        del x, w, b, qx, qw, qr, dr, w1, b1, qw1, w2, b2, h, qh, sh, qw2
 
 
 if __name__ == "__main__":
