@@ -678,6 +678,28 @@ std::tuple<at::Tensor, at::Tensor> quant_e4m3(at::Tensor x) {
   return {q, ws.narrow(0, 1, 1)};
 }
 
+// every segment of `table` (int64 [n, 4]: first chunk, offset in params, offset in q_arena, element count) quantised
+// as quant_e4m3 would: bytes into the uint8 q_arena, max |x| bits into amax[t] (int32 [n]), 2^−e into dscale[t]
+// (float32 [n]); three launches, no host sync.  `host` as transpose_batched's: the entries are validated there.
+void quant_e4m3_grouped(at::Tensor params, at::Tensor q_arena, at::Tensor amax, at::Tensor dscale, at::Tensor table,
+                        at::Tensor host, int64_t chunks) {
+  CHECK_IN(params); CHECK_IN(q_arena); CHECK_IN(amax); CHECK_IN(dscale); CHECK_IN(table); CHECK_BF16(params); CHECK_F32(dscale);
+  TORCH_CHECK(q_arena.scalar_type() == at::kByte && amax.scalar_type() == at::kInt, "q_arena: uint8, amax: int32");
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 4 && table.size(0) > 0 &&
+              table.size(0) < (1LL << 31), "table: int64 [n, 4]");
+  TORCH_CHECK(!host.is_cuda() && host.scalar_type() == at::kLong && host.is_contiguous() &&
+              host.sizes() == table.sizes(), "quant_e4m3_grouped: host table must mirror the device table");
+  const int64_t n = table.size(0);
+  TORCH_CHECK(amax.numel() == n && dscale.numel() == n, "quant_e4m3_grouped: amax and dscale take one word per table row");
+  CHECK_ALIGN16(params);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q_arena.data_ptr()) % 8 == 0, "q_arena must be 8-B aligned");
+  CHECK_RC(pdo::quant_e4m3_grouped(bp(params), params.numel(), q_arena.data_ptr<uint8_t>(), q_arena.numel(),
+                                   reinterpret_cast<unsigned*>(amax.data_ptr<int32_t>()), fp(dscale),
+                                   reinterpret_cast<const long long*>(table.data_ptr<int64_t>()),
+                                   reinterpret_cast<const long long*>(host.data_ptr<int64_t>()), (int)n, chunks,
+                                   cur_stream()), "quant_e4m3_grouped");
+}
+
 bool gemm_nt_f8_supported(int64_t M, int64_t N, int64_t K) {
   return M < (1LL << 31) && N < (1LL << 31) && K < (1LL << 31) &&
          pdo::gemm_nt_f8_ok((int)M, (int)N, (int)K, (int)K, (int)K, (int)N);
@@ -1929,6 +1951,9 @@ PYBIND11_MODULE(_pdo_hip, m) {
   }, py::arg("on") = -1, "gemm_nt4 tile order: 1 = dynamic per-XCD counters, 0 = static (default); returns the previous");
   m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(), py::arg("out") = py::none());
   m.def("quant_e4m3", &quant_e4m3, py::arg("x"));
+  m.def("quant_e4m3_grouped", &quant_e4m3_grouped, py::arg("params"), py::arg("q_arena"), py::arg("amax"),
+        py::arg("dscale"), py::arg("table_dev"), py::arg("table_host"), py::arg("chunks"));
+  m.attr("QUANT_GROUP_CHUNK") = pdo::QUANT_GROUP_CHUNK;
   m.def("gemm_nt_f8_supported", &gemm_nt_f8_supported);
   m.def("gemm_nt_f8", &gemm_nt_f8, py::arg("qa"), py::arg("da"), py::arg("qb"), py::arg("db"), py::arg("bias") = py::none());
   m.def("gemm_nt_f8_gelu", &gemm_nt_f8_gelu, py::arg("qa"), py::arg("da"), py::arg("qb"), py::arg("db"), py::arg("bias"),

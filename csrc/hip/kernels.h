@@ -234,6 +234,17 @@ int gemm_nt_get_impl();
 int amax_bf16(const bf16* x, long long rows, long long cols, long long ld, unsigned* amax_out, hipStream_t st);
 int quant_e4m3(const bf16* x, long long rows, long long cols, long long ld, const unsigned* amax, unsigned char* q,
                long long ldq, float* dscale_out, hipStream_t st);
+// The same pair over a table of n segments of one bf16 arena, three launches in all (clear n amax words, amax,
+// convert): table = n × {first chunk, src offset, dst offset, count} int64, offsets in elements of src / bytes of q;
+// segment t takes ⌈count / QUANT_GROUP_CHUNK⌉ chunks (one workgroup each) and gets amax[t] (a float's bits),
+// dscale[t] = 2^−e and its bytes at q + dst, exactly what amax_bf16 + quant_e4m3 give for src[offset .. + count).
+// Checked on table_host, the host copy the device table was made from (no device → host copy): rows sorted and
+// contiguous by first chunk from 0, offsets and counts multiples of 8 (count ≥ 8), the chunk total = chunks < 2^31:
+// else -2; a segment outside [0, src_n) / [0, q_n): -3; nothing launched.  src 16-B, q 8-B aligned.
+constexpr int QUANT_GROUP_CHUNK = 8192;
+int quant_e4m3_grouped(const bf16* src, long long src_n, unsigned char* q, long long q_n, unsigned* amax, float* dscale,
+                       const long long* table_dev, const long long* table_host, int n, long long chunks,
+                       hipStream_t st);
 // gemm_nt_f8.hip: C[M][N] = bf16((A[M][K]·B[N][K]ᵀ)·da·db (+ bias[N])), A / B e4m3 bytes, da / db device floats, fp32
 // accumulation, one rounding.  M % 256 = 0, N % 256 ∈ {0, 128}, K % 256 = 0 (≥ 256), lda / ldb % 16 = 0 and ≥ K
 // (A, B 16-B aligned), ldc % 4 = 0 and ≥ N: else -2, nothing launched.  epi: EPI_PLAIN or EPI_BIAS (-3 without bias);

@@ -18,6 +18,28 @@
 // normal.  x·s is exact in fp32 and the hardware convert (v_cvt_pk_fp8_f32,
 // OCP e4m3fn on gfx950) rounds to nearest even: 16 B of bf16 in, 8 B of fp8 out
 // per lane.  Only finite inputs are specified.
+//
+// Grouped form (quant_e4m3_grouped): the same two passes over a TABLE of segments of
+// one bf16 arena — the step's FP8 weights, quantised once per optimizer step instead
+// of three small launches in front of every GEMM — into one compact byte arena, with
+// one amax word and one scale per segment.  Three launches for any number of tensors:
+// clear the n amax words, amax, convert.
+//
+// Split of the work: one workgroup per CHUNK (GCH = 8192 elements, 16 KiB of bf16) of
+// one tensor, not a persistent grid-stride loop.  A chunk never spans two tensors, so
+// a workgroup finds its table row once (binary search on the first-chunk column, as
+// transpose_bf16_batched does), reduces to ONE amax word and needs no per-vector row
+// lookup; a grid-stride loop over chunks would repeat the search and the LDS reduction
+// per chunk to save only the workgroup launch, which at 16 KiB in and 8 KiB out per
+// workgroup is small beside the traffic.  GPT-2-medium's sets are 20,480 ("ln") to
+// 32,256 ("lnmx") chunks: ≥ 80 workgroups per CU, so the tail is short.  Each lane
+// issues its four 16-B loads (one per 256-lane stripe of the chunk, coalesced) before
+// the first use; vectors past the tensor's end (only in its last chunk) are skipped.
+// amax: packed u16 max per lane → wave (shuffles) → workgroup (4 words of LDS) → one
+// atomicMax per workgroup.  Nothing waits on another workgroup inside a launch; the
+// convert launch reads the finished amax words.  The convert workgroup of a tensor's
+// chunk 0 writes its 2^−e.  Same f8_scale_exp and f8_cvt8 on the same bf16 values as
+// the per-tensor pair, and a max is order-free: the bytes and scales are identical.
 #include "common.h"
 #include "f8_quant.h"
 #include "kernels.h"
@@ -100,7 +122,105 @@ Launch plan(long long rows, long long cols, long long ld, long long ldq) {
   return {(unsigned)nvec, RowMap{(unsigned)(vpr ? vpr : 1), ld, ldq}, (int)(cols % 8), stream_grid(nvec, NTHR * 4)};
 }
 
+// ---- grouped form: a table of arena segments, one workgroup per chunk (file header) ----
+constexpr int GCH = QUANT_GROUP_CHUNK;  // elements per chunk
+constexpr int GVC = GCH / 8;            // 16-B vectors per chunk
+constexpr int GLD = GVC / NTHR;         // 16-B loads per lane, all issued before the first use
+static_assert(GLD * NTHR * 8 == GCH && GLD >= 2, "a chunk is a whole number of 256-lane stripes");
+
+__global__ void clear_words_kernel(unsigned* p, int n) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0u;
+}
+
+// what chunk b covers: its tensor t (the row whose first chunk is the last one ≤ b), the tensor's element offsets
+// in the bf16 and the byte arena, the chunk's first 16-B vector inside the tensor and the tensor's vector count
+struct Seg {
+  int t;
+  long long src, dst, v0, nvec;
+};
+__device__ __forceinline__ Seg find_seg(const long long* __restrict__ table, int n, long long b) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[4 * mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const long long* e = table + 4 * lo;
+  return {lo, e[1], e[2], (b - e[0]) * GVC, e[3] / 8};
+}
+
+// the lane's GLD vectors of the chunk (stripe i: vector v0 + i·NTHR + lane); zeros past the tensor's end
+template <typename V>
+__device__ __forceinline__ void load_chunk(const V* __restrict__ x, const Seg& s, V (&b)[GLD]) {
+  const long long v = s.v0 + threadIdx.x;
+  if (s.v0 + GVC <= s.nvec) {  // a whole chunk (uniform branch): unconditional loads, back to back
+#pragma unroll
+    for (int i = 0; i < GLD; ++i) b[i] = x[v + i * NTHR];
+  } else {
+#pragma unroll
+    for (int i = 0; i < GLD; ++i) b[i] = v + i * NTHR < s.nvec ? x[v + i * NTHR] : V{};
+  }
+}
+
+__global__ __launch_bounds__(NTHR) void amax_grouped_kernel(const bf16* __restrict__ src,
+                                                            const long long* __restrict__ table, int n,
+                                                            unsigned* __restrict__ amax) {
+  __shared__ unsigned red[NTHR / WAVE];
+  const Seg s = find_seg(table, n, blockIdx.x);
+  u16x8 b[GLD];
+  load_chunk(reinterpret_cast<const u16x8*>(src + s.src), s, b);
+  u16x8 m = b[0] & (unsigned short)0x7fff;
+#pragma unroll
+  for (int i = 1; i < GLD; ++i) m = __builtin_elementwise_max(m, b[i] & (unsigned short)0x7fff);
+  unsigned r = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) r = max(r, (unsigned)m[k]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) r = max(r, (unsigned)__shfl_xor((int)r, o, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < NTHR / WAVE; ++w) r = max(r, red[w]);
+    if (r) atomicMax(amax + s.t, r << 16);
+  }
+}
+
+__global__ __launch_bounds__(NTHR) void quant_grouped_kernel(const bf16* __restrict__ src,
+                                                             const long long* __restrict__ table, int n,
+                                                             const unsigned* __restrict__ amax,
+                                                             unsigned char* __restrict__ q, float* __restrict__ dscale) {
+  const Seg s = find_seg(table, n, blockIdx.x);
+  bf16x8 b[GLD];
+  load_chunk(reinterpret_cast<const bf16x8*>(src + s.src), s, b);
+  const int e = f8_scale_exp(amax[s.t]);
+  const float sc = f8_pow2(e);
+  if (s.v0 == 0 && threadIdx.x == 0) dscale[s.t] = f8_pow2(-e);
+  i32x2* out = reinterpret_cast<i32x2*>(q + s.dst);
+  const long long v = s.v0 + threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < GLD; ++i)
+    if (v + i * NTHR < s.nvec) out[v + i * NTHR] = f8_cvt8(to_f32(b[i]) * sc);
+}
+
 }  // namespace
+
+int quant_e4m3_grouped(const bf16* src, long long src_n, unsigned char* q, long long q_n, unsigned* amax, float* dscale,
+                       const long long* table_dev, const long long* table_host, int n, long long chunks,
+                       hipStream_t st) {
+  if (n < 1 || chunks < 1 || chunks > 0x7fffffffLL) return -2;
+  long long want = 0;
+  for (const long long* e = table_host; e != table_host + 4ll * n; e += 4) {
+    if (e[0] != want || e[3] < 8 || e[3] % 8 || e[1] % 8 || e[2] % 8) return -2;
+    if (e[1] < 0 || e[1] > src_n - e[3] || e[2] < 0 || e[2] > q_n - e[3]) return -3;
+    want += (e[3] + GCH - 1) / GCH;
+  }
+  if (want != chunks) return -2;
+  clear_words_kernel<<<(n + NTHR - 1) / NTHR, NTHR, 0, st>>>(amax, n);
+  amax_grouped_kernel<<<(unsigned)chunks, NTHR, 0, st>>>(src, table_dev, n, amax);
+  quant_grouped_kernel<<<(unsigned)chunks, NTHR, 0, st>>>(src, table_dev, n, amax, q, dscale);
+  return 0;
+}
 
 int amax_bf16(const bf16* x, long long rows, long long cols, long long ld, unsigned* amax_out, hipStream_t st) {
   if (!shape_ok(rows, cols, ld, cols)) return -2;

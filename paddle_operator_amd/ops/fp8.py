@@ -35,7 +35,9 @@ A third form, for an operand whose producer never sees a whole row:
   the scaled MFMA, adding fc2's bias and the residual stream in its epilogue (``ops.mlp(mx=True)``,
   ``ops.mlp_add_layer_norm(mx=True)``).  The bf16 output is still stored: the backward and fc2's dW read it.
 
-The weight is quantised per tensor, per call, in all three.
+The weight is quantised per tensor in all three: once per optimizer step for the weights a trainer registered
+(``parallel.flat.FlatParams.enable_wq``: one grouped launch pair when ``wt_scope`` opens, the e4m3 bytes and scale
+read from the arena while it is live), just in time per call everywhere else — the same bytes (``_weight_e4m3``).
 """
 from __future__ import annotations
 
@@ -75,6 +77,25 @@ def ref_linear_fp8(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = No
     return y.to(x.dtype).to(x.device)
 
 
+# the e4m3 weights of a trainer's step taken from the arena (FlatParams.enable_wq) instead of quantised per call; read
+# when wt_scope opens.  Same bits either way (tests/test_fp8_wq_gpu.py); measured in profiles/fp8_wq.md
+_WQ_ARENA = [True]
+
+
+def _live_wq(w):
+    """The arena's e4m3 copy (q, 2^−e) of ``w`` (parallel.flat.FlatParams.enable_wq) while it is live (inside the
+    trainer's wt_scope), else None."""
+    t = getattr(w, "_pdo_wq", None)
+    if t is not None and t[0].wq_live:
+        return t[1], t[2]
+    return None
+
+
+def _weight_e4m3(w):
+    """(q, 2^−e) of the weight ``w``: the step's arena copy while live, else quantised just in time."""
+    return _live_wq(w) or _native.require_hip().quant_e4m3(w)
+
+
 def _f8_ok(x, w, b) -> bool:
     return (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.is_contiguous()
             and w.is_contiguous() and w.dim() == 2 and (b is None or b.dtype == torch.bfloat16)
@@ -82,13 +103,13 @@ def _f8_ok(x, w, b) -> bool:
 
 
 def _fwd_gemm_f8(x, w, b=None):
-    """x·Wᵀ (+ b) with both operands quantised to e4m3 just in time: two quantiser launches per operand, then
-    gemm_nt_f8 with the bias in its epilogue.  Outside its shape contract: ``_fwd_gemm``, the bf16 product."""
+    """x·Wᵀ (+ b) with both operands as e4m3: x quantised just in time (two quantiser launches), W by
+    ``_weight_e4m3``, then gemm_nt_f8 with the bias in its epilogue.  Outside its shape contract: ``_fwd_gemm``, the bf16 product."""
     if not _f8_ok(x, w, b):
         return _fwd_gemm(x, w, b)
     m = _native.require_hip()
     qx, dx = m.quant_e4m3(x.reshape(-1, x.shape[-1]))
-    qw, dw = m.quant_e4m3(w)
+    qw, dw = _weight_e4m3(w)
     return m.gemm_nt_f8(qx, dx, qw, dw, b).view(*x.shape[:-1], w.shape[0])
 
 
@@ -149,9 +170,9 @@ def _rows_ok(q, d, w, b=None) -> bool:
 
 def _fwd_gemm_f8_rows(q, d, w, b=None):
     """[rows, N] = (q·Wᵀ)·d[row]·dw (+ b): q, d the LayerNorm's rows and per-token scales, W quantised per
-    tensor just in time as ``_fwd_gemm_f8`` does; the caller has checked ``_rows_ok``."""
+    tensor (``_weight_e4m3``) as ``_fwd_gemm_f8`` does; the caller has checked ``_rows_ok``."""
     m = _native.require_hip()
-    qw, dw = m.quant_e4m3(w)
+    qw, dw = _weight_e4m3(w)
     return m.gemm_nt_f8(q, d, qw, dw, b)
 
 
@@ -234,5 +255,5 @@ def _fwd_gemm_mx8(q, s, w, b=None, res=None):
     """[rows, N] = (q·2^(s − 127))·Wᵀ·dw (+ b) (+ res): q, s the MXFP8 rows fc1's epilogue wrote, W quantised per
     tensor just in time as ``_fwd_gemm_f8_rows`` does; the caller has checked ``_mx_ok``."""
     m = _native.require_hip()
-    qw, dw = m.quant_e4m3(w)
+    qw, dw = _weight_e4m3(w)
     return m.gemm_nt_mx8(q, s, qw, dw, b, None if res is None else res.reshape(-1, w.shape[0]))

@@ -67,6 +67,22 @@ def _noop_ready(p):
     return None
 
 
+WQ_CHUNK = 8192  # elements one workgroup of quant_e4m3_grouped takes (csrc/hip/kernels.h QUANT_GROUP_CHUNK)
+
+
+def wq_table(segs):
+    """The table of ``quant_e4m3_grouped`` for ``segs`` = (offset in the bf16 arena, element
+    count) per tensor, in arena order: rows (first chunk, source offset, offset in the compact
+    byte arena, count), the chunk total and the byte arena's size.  Destinations are packed in
+    row order, each on a 16-byte boundary (the FP8 GEMMs' operand alignment)."""
+    rows, chunk, dst = [], 0, 0
+    for off, n in segs:
+        rows.append((chunk, off, dst, n))
+        chunk += (n + WQ_CHUNK - 1) // WQ_CHUNK
+        dst = _round_up(dst + n, 16)
+    return rows, chunk, dst
+
+
 class AuxGrad:
     """Second gradient slot of a ``split`` parameter (see module docstring).
 
@@ -224,9 +240,36 @@ class FlatParams:
         for (_, off, _, R, C) in rows:
             by_off[off].param._pdo_wt = (self, self.wt[off:off + R * C].view(C, R))
 
+    def enable_wq(self, params):
+        """An e4m3 copy of each of ``params`` (2-D contiguous bf16 weights of this arena,
+        whole 16-B vectors) with its per-tensor scale, for the FP8 forward GEMMs: all of
+        them quantised by ONE grouped launch pair per step (``wt_scope``) instead of
+        three small launches per weight per forward per micro-batch.  Each covered
+        parameter gets ``_pdo_wq = (arena, e4m3 bytes [N, K], 2^−e as float32[1])``,
+        read only while ``arena.wq_live``.  Derived state: never checkpointed.  A no-op
+        off the GPU or off bf16, as ``enable_wt``."""
+        self.wq, self.wq_live = None, False
+        by_id = {id(s.param): s for s in self.slots}
+        slots = sorted((by_id[id(p)] for p in params), key=lambda s: s.offset)
+        if not slots or self.device.type != "cuda" or self.dtype != torch.bfloat16:
+            return
+        bad = [s.name for s in slots if len(s.shape) != 2 or not s.param.is_contiguous() or s.numel % 8]
+        if bad:
+            raise ValueError(f"enable_wq takes 2-D contiguous weights of a multiple of 8 elements, not {bad}")
+        rows, chunks, nbytes = wq_table([(s.offset, s.numel) for s in slots])
+        self.wq = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.wq_amax = torch.zeros(len(rows), dtype=torch.int32, device=self.device)
+        self.wq_dscale = torch.ones(len(rows), dtype=torch.float32, device=self.device)
+        self._wq_host = torch.tensor(rows, dtype=torch.int64)
+        self._wq_dev = self._wq_host.to(self.device)
+        self._wq_chunks = chunks
+        for t, (s, (_, _, dst, n)) in enumerate(zip(slots, rows)):
+            s.param._pdo_wq = (self, self.wq[dst:dst + n].view(s.shape), self.wq_dscale[t:t + 1])
+
     def wt_scope(self):
-        """Build every Wᵀ (one launch) and mark them live for the scope: the
-        trainer's forward + backward, where the weights do not change."""
+        """Build every Wᵀ (one launch) and every e4m3 weight (``enable_wq``, one grouped
+        launch pair; skipped with ``ops.fp8._WQ_ARENA`` off) and mark them live for the
+        scope: the trainer's forward + backward, where the weights do not change."""
         flat = self
 
         class _Scope:
@@ -236,9 +279,17 @@ class FlatParams:
                     _native.require_hip().transpose_batched(flat.params, flat.wt, flat._wt_dev, flat._wt_host,
                                                             flat._wt_tiles)
                     flat.wt_live = True
+                if getattr(flat, "wq", None) is not None:
+                    from .. import _native
+                    from ..ops.fp8 import _WQ_ARENA
+                    if _WQ_ARENA[0]:
+                        _native.require_hip().quant_e4m3_grouped(flat.params, flat.wq, flat.wq_amax, flat.wq_dscale,
+                                                                 flat._wq_dev, flat._wq_host, flat._wq_chunks)
+                        flat.wq_live = True
 
             def __exit__(self, *exc):
                 flat.wt_live = False
+                flat.wq_live = False
 
         return _Scope()
 

@@ -86,6 +86,15 @@ def derive_dropout_seed(dropout_seed: int, rank: int) -> int:
     return z ^ (z >> 31)
 
 
+def fp8_weights(model, fp8: str) -> list:
+    """The weights whose forward product runs on e4m3 under ``GPT2Config.fp8 = fp8``, per block: QKV's
+    ("qkv"), fc1's as well ("ln"), fc2's as well ("lnmx") — those the grouped quantiser takes (2-D,
+    contiguous, whole 16-B vectors; FlatParams.enable_wq)."""
+    per_block = {"off": (), "qkv": ("qkv",), "ln": ("qkv", "fc"), "lnmx": ("qkv", "fc", "fc_proj")}[fp8]
+    ws = [getattr(blk, name).weight for blk in model.blocks for name in per_block]
+    return [w for w in ws if w.dim() == 2 and w.is_contiguous() and w.numel() % 8 == 0]
+
+
 # test hook (not a user knob): False adds every micro-batch of an accumulated step
 # straight into the bf16 arena, without the fp32 accumulator
 _ACCUM_FP32 = [True]
@@ -144,6 +153,9 @@ class GPT2Trainer:
                                split=split)
         # every dX GEMM's Wᵀ operand built in one launch per step (wt_scope)
         self.flat.enable_wt()
+        # and, under cfg.fp8, the e4m3 weights its FP8 GEMMs read, in one grouped launch pair per step
+        if cfg.fp8 != "off":
+            self.flat.enable_wq(fp8_weights(model, cfg.fp8))
         self.ddp = BucketedDDP(self.flat)
         self.opt = FlatAdamW(self.flat, lr=lr)
         self.gen = torch.Generator(device=self.device)

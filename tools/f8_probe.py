@@ -19,6 +19,14 @@ layer = (f8_fc1_mx − f8_fc1) + quantise W2 + mx8_fc2 − nt4_fc2.
     python tools/f8_probe.py --step 64 [--model gpt2-medium] [--steps 8] [--rounds 3]   # step time, off / qkv / ln / lnmx
     python tools/f8_probe.py --losses 40 [--micro-batch 8]                              # losses of the modes
 
+    python tools/f8_probe.py --wq 64 [--grad-accum 1] [--model gpt2-medium] [--steps 8] [--rounds 3]   # profiles/fp8_wq.md
+
+--wq: the step's e4m3 weights from the arena (FlatParams.enable_wq) against just in time, for fp8 = ln and lnmx: the
+grouped launch pair over the mode's whole weight set against the summed per-tensor quant_e4m3 calls it replaces
+(device events), then the step time with ops.fp8._WQ_ARENA off and on in interleaved rounds on one trainer, and the
+peak device memory without and with the byte arena.  The per-width rows carry quant_w_grouped: one layer's three
+weights in one grouped pair, beside quant_w + quant_w1 + quant_w2.
+
 --step: one trainer, GPT2Config.fp8 switched between rounds (host clock around a device synchronise, warm-up for
 every mode).  --losses: a fresh trainer per mode, same seed, synthetic stream, lr 3e-4.
 """
@@ -80,6 +88,93 @@ def step_times(a):
     print(json.dumps(rec), flush=True)
 
 
+def _grouped(m, ws):
+    """(call, elements): the grouped quantiser over the bf16 matrices ``ws`` laid out as one arena."""
+    from paddle_operator_amd.parallel.flat import ALIGN, wq_table
+    segs, off = [], 0
+    for w in ws:
+        segs.append((off, w.numel()))
+        off = (off + w.numel() + ALIGN - 1) // ALIGN * ALIGN
+    arena = torch.zeros(off, device=ws[0].device, dtype=torch.bfloat16)
+    for (o, n), w in zip(segs, ws):
+        arena[o:o + n] = w.reshape(-1)
+    rows, chunks, nbytes = wq_table(segs)
+    host = torch.tensor(rows, dtype=torch.int64)
+    dev = host.to(arena.device)
+    q = torch.empty(nbytes, device=arena.device, dtype=torch.uint8)
+    amax = torch.zeros(len(rows), device=arena.device, dtype=torch.int32)
+    d = torch.zeros(len(rows), device=arena.device)
+    return (lambda: m.quant_e4m3_grouped(arena, q, amax, d, dev, host, chunks)), sum(n for _, n in segs)
+
+
+def wq_times(a):
+    import gc
+    import time
+    from paddle_operator_amd.models.gpt2 import GPT2Config
+    from paddle_operator_amd.ops import fp8
+    from paddle_operator_amd.train import GPT2Trainer, fp8_weights
+    m = _native.require_hip()
+    dev = torch.device("cuda", 0)
+    for mode in ("ln", "lnmx"):
+        rec = {"model": a.model, "fp8": mode, "micro_batch": a.wq, "grad_accum": a.grad_accum, "seq": a.seq, "steps": a.steps}
+        mem = {}
+        for arena in (False, True):  # without: built with fp8 off, the mode set afterwards (no enable_wq)
+            gc.collect()  # the previous trainer (its parameters point back at its arena) before its blocks are reused
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            cfg = GPT2Config.named(a.model)
+            cfg.fp8 = mode if arena else "off"
+            tr = GPT2Trainer(cfg, a.wq, a.seq, dev, lr=3e-4, seed=0, grad_accum=a.grad_accum)
+            tr.cfg.fp8 = mode
+            for _ in range(3):
+                tr.step()
+            torch.cuda.synchronize()
+            mem[arena] = torch.cuda.max_memory_allocated() / 2 ** 30
+            if not arena:
+                tr.close()
+                del tr
+        rec["max_mem_gb_without"], rec["max_mem_gb_with"] = round(mem[False], 3), round(mem[True], 3)
+        rec["arena_gb"] = round(tr.flat.wq.numel() / 2 ** 30, 3)
+        # the kernels: the trainer's own table against one quant_e4m3 per covered weight
+        ws = fp8_weights(tr.model, mode)
+        n = sum(w.numel() for w in ws)
+        fl = tr.flat
+        fns = {"grouped": lambda: m.quant_e4m3_grouped(fl.params, fl.wq, fl.wq_amax, fl.wq_dscale, fl._wq_dev, fl._wq_host,
+                                                       fl._wq_chunks),
+               "per_tensor": lambda: [m.quant_e4m3(w) for w in ws]}
+        kt = {k: [] for k in fns}
+        for _ in range(a.rounds):
+            for k, fn in fns.items():
+                kt[k].append(bench(fn, a.iters))
+        rec["tensors"], rec["elements"] = len(ws), n
+        for k, v in kt.items():
+            rec[k + "_us"] = [round(t, 1) for t in v]
+        # bytes the pair needs: two reads of the bf16 values and one write of the bytes
+        rec["grouped_TBps"] = round(5.0 * n / statistics.median(kt["grouped"]) / 1e6, 3)
+        times, peak = {False: [], True: []}, {False: [], True: []}
+        for rnd in range(a.rounds + 1):  # round 0: warm-up of both
+            for hook in (False, True):
+                fp8._WQ_ARENA[0] = hook
+                tr.step()
+                if rnd == 0:
+                    continue
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    tr.step()
+                torch.cuda.synchronize()
+                times[hook].append((time.perf_counter() - t0) / a.steps * 1e3)
+                peak[hook].append(round(torch.cuda.max_memory_allocated() / 2 ** 30, 3))
+        fp8._WQ_ARENA[0] = True
+        rec["jit_ms"], rec["arena_ms"] = ([round(t, 3) for t in times[h]] for h in (False, True))
+        # the same trainer (byte arena allocated either way): what the path alone does to the peak
+        rec["jit_peak_gb"], rec["arena_peak_gb"] = peak[False], peak[True]
+        print(json.dumps(rec), flush=True)
+        tr.close()
+        del tr, ws, fl, fns
+
+
 def losses(a):
     for k in MODES:
         tr = _trainer(a.model, a.micro_batch, a.seq)
@@ -100,6 +195,8 @@ def main():
     ap.add_argument("--widths", default="768,1024,1280")
     ap.add_argument("--step", type=int, default=0, metavar="MICRO_BATCH", help="time the training step instead")
     ap.add_argument("--losses", type=int, default=0, metavar="STEPS", help="print the modes' losses instead")
+    ap.add_argument("--wq", type=int, default=0, metavar="MICRO_BATCH", help="time the step's e4m3 weight arena instead")
+    ap.add_argument("--grad-accum", type=int, default=1)
     ap.add_argument("--model", default="gpt2-medium")
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--seq", type=int, default=1024)
@@ -109,6 +206,8 @@ def main():
         return step_times(a)
     if a.losses:
         return losses(a)
+    if a.wq:
+        return wq_times(a)
     m = _native.require_hip()
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0)
@@ -137,8 +236,10 @@ def main():
         b2 = torch.empty(C, device=dev, dtype=torch.bfloat16).uniform_(-0.1, 0.1, generator=g)
         _, h, qh, sh = m.gemm_nt_f8_gelu(qr, dr, qw1, dw1, b1, mx=True)
         qw2, dw2 = m.quant_e4m3(w2)
+        grouped, _ = _grouped(m, [w, w1, w2])
 
-        fns = {"f8_gemm": lambda: m.gemm_nt_f8(qx, dx, qw, dw, b), "quant_x": lambda: m.quant_e4m3(x),
+        fns = {"quant_w_grouped": grouped,  # one layer's three weights: against quant_w + quant_w1 + quant_w2
+               "f8_gemm": lambda: m.gemm_nt_f8(qx, dx, qw, dw, b), "quant_x": lambda: m.quant_e4m3(x),
                "quant_w": lambda: m.quant_e4m3(w), "f8_whole": whole, "nt4": lambda: m.gemm_nt(x, w, b),
                "ln": lambda: m.layernorm_fwd(x, lw, lb, 1e-5), "ln_q8": lambda: m.layernorm_fwd(x, lw, lb, 1e-5, True),
                "f8_rows": lambda: m.gemm_nt_f8(qr, dr, qw, dw, b), "quant_w1": lambda: m.quant_e4m3(w1),
